@@ -1,6 +1,7 @@
 """Benchmark: geometric-median aggregations/sec at K=1000, d=11M (BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload c3|c4-shard|c2|...]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...     (the driver's N>1 form)
 
 One step = one full aggregation: for the default workload (BASELINE config C3)
@@ -21,10 +22,17 @@ is fixed, so scaling is "strong".  value = aggregations/s of the whole job.
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the fused
 streaming pass: 4*K*d_local algorithmic bytes per launch) with HIP events the
 library records around every launch on its stream, and the whole aggregation
-(4*K*d_local*(passes) / ms_per_step); `cpu_baseline` times the CPU oracle (an
-op-for-op PyTorch-CPU restatement of the reference's gm2 / gm) on a bounded
-sample on this host; `check` is a full-size correctness check of the returned
-aggregate (the fp64 Weiszfeld fixed-point step at g, all ranks).
+(4*K*d_local*(passes) / ms_per_step).
+
+A plain run sets up, warms up, times `--steps` aggregations and prints the line.
+`--dump-outputs DIR` also writes what the last timed step returned (the aggregate
+and its iteration count) as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.  `--full` adds the legs that take runs of their
+own (null in a plain run's line): `cpu_baseline` times the CPU oracle (an op-for-op
+PyTorch-CPU restatement of the reference's gm2 / gm) on a bounded sample on this
+host; `check` is a full-size correctness check of the returned aggregate (the fp64
+Weiszfeld fixed-point step at g, all ranks); `alt_layout` times the other layout
+(c5: the other reading); `soak` keeps the GPU busy for an outside sampler.
 """
 from __future__ import annotations
 
@@ -64,6 +72,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=None, help="default 20 (c5: 2 sweeps)")
     p.add_argument("--warmup", type=int, default=None, help="default 3 (c5: 1 sweep)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs a plain run leaves out: the soak, "
+                        "the other layout's (c5: the other reading's) measurement, the full-size "
+                        "correctness check and the CPU baseline (--soak / --alt-steps / --no-check "
+                        "/ --no-cpu still trim them)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32; a "
+                        "fixed seeded sample of anything over the 64 MB budget)")
     p.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     p.add_argument("--algo", default="auto", choices=["auto", "stream", "twopass", "gram", "gram_f32"])
     p.add_argument("--agg", default=None, choices=["gm2", "gm"],
@@ -76,8 +92,8 @@ def parse():
     p.add_argument("--layout", default="auto", choices=["auto", "rows", "panels"],
                    help="client matrix layout: rows = the reference's [K, d] stack; panels = "
                         "ClientPanels [ceil(d/W)][K][W] (streaming algorithm); auto = panels "
-                        "for the streaming workloads (c3), rows otherwise.  The other layout "
-                        "is timed too (alt_layout in the JSON line).")
+                        "for the streaming workloads (c3), rows otherwise.  With --full the other "
+                        "layout is timed too (alt_layout in the JSON line).")
     p.add_argument("--alt-steps", type=int, default=None,
                    help="steps for the other layout's measurement (0 = skip)")
     p.add_argument("--separate-oma", action="store_true",
@@ -212,6 +228,28 @@ def columns(src, c0, c1):
     p0, p1 = c0 // W, -(-c1 // W)
     blk = src.data[p0:p1].permute(1, 0, 2).reshape(src.K, (p1 - p0) * W)
     return blk[:, c0 - p0 * W:c1 - p0 * W]
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(dirpath, arrays, suffix=""):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as DIR/<name><suffix>.npy
+    in float32, DUMP_BUDGET_BYTES in all.  The budget is shared smallest array first (what
+    one leaves goes to the larger ones); an array over its share is written as a sample of
+    its flattened elements: sorted indices drawn without replacement by numpy's
+    default_rng(0) from (numel, share), the same for every run and every build."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    left, todo = DUMP_BUDGET_BYTES // 4, len(arrays)            # float32 elements, arrays
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        t = t.detach()
+        share = left // todo
+        left, todo = left - min(share, t.numel()), todo - 1
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), t.to(torch.float32).cpu().numpy())
 
 
 def fixed_point_step(X, g: torch.Tensor, allreduce=None, cols=1 << 20):
@@ -441,8 +479,12 @@ def run_c5(args, json_out, rank=0, world=1):
         return total, pass_ms, launches, iters, groups_out
 
     total, pass_ms, launches, iters, per_group = measure(args.reading, args.steps, args.warmup)
+    if args.dump_outputs:
+        arrays = {f"aggregate_var{vi}_q{c0}": out for (vi, c0), (out, _) in outs.items()}
+        arrays["iters"] = torch.tensor(iters, dtype=torch.float32)
+        dump_outputs(args.dump_outputs, arrays, f"_rank{rank}" if world > 1 else "")
     check = c5_check(groups, outs, args.reading, args.maxiter, recipe_of(args.reading)) \
-        if not args.no_check else None
+        if args.full and not args.no_check else None
     n_prob = len(iters)                          # this rank's problems
     n_total = per_var * len(C5_VARS)             # the sweep's, over every rank
     mean_it = sum(iters) / n_prob
@@ -451,7 +493,7 @@ def run_c5(args, json_out, rank=0, world=1):
     agg_bytes = sum(i + 1 for i in iters) * 4.0 * K * d
     alt_reading = "aircomp" if args.reading == "prenoise" else "prenoise"
     alt = None
-    if args.alt_steps != 0 and world == 1:
+    if args.full and args.alt_steps != 0 and world == 1:
         a_total, _, _, a_iters, a_groups = measure(alt_reading, 1, 0)
         alt = {"reading": alt_reading, "recipe": recipe_of(alt_reading),
                "value": len(a_iters) / a_total, "seconds": a_total,
@@ -533,7 +575,7 @@ def run_c5(args, json_out, rank=0, world=1):
             "aggregation_frac_def": "sum_p 4*K*d*(iters_p+1) / ms_per_step / 8 TB/s "
                                     "(OMA pre-noise time included, its bytes not)"}
     cpu = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         vi0, _, c00, X0, g00, _ = groups[0]
         if X0 is None:                       # problem 0's clean rows, regenerated
             fill_problem(vi0, c00, 0, tmp, g00[0], recipe_of(args.reading))
@@ -942,10 +984,14 @@ def main():
 
     elapsed, pass_ms, launches, res, out = measure(inputs(layout), args.steps, args.warmup)
     passes = 2 if res.algo.startswith("gram") else res.iters + 1
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     {"aggregate": out, "iters": torch.tensor([res.iters], dtype=torch.float32)},
+                     f"_rank{rank}" if world > 1 else "")
     # untimed soak: the same aggregation repeated for ~args.soak seconds (a count every
     # rank derives from the max-over-ranks time, so collectives stay in lockstep)
     soak = None
-    if args.soak > 0:
+    if args.full and args.soak > 0:
         n_soak = int(args.soak / max(elapsed / args.steps, 1e-6))
         t0 = time.perf_counter()
         for _ in range(n_soak):
@@ -956,9 +1002,9 @@ def main():
     alt = None
     alt_layout = "rows" if layout == "panels" else "panels"
     alt_steps = args.alt_steps if args.alt_steps is not None else max(3, args.steps // 4)
-    if alt_steps > 0 and not big and (alt_layout == "rows" or (args.algo in ("auto", "stream", "gram")
-                                                   and bz.panel_width(K) > 0
-                                                   and d_total >= 1 << 20)):
+    if args.full and alt_steps > 0 and not big and (
+            alt_layout == "rows" or (args.algo in ("auto", "stream", "gram")
+                                     and bz.panel_width(K) > 0 and d_total >= 1 << 20)):
         a_el, a_ms, a_n, a_res, _ = measure(inputs(alt_layout), alt_steps, 1)
         a_pass = (a_ms / 1e3) / max(a_n, 1)
         a_passes = 2 if a_res.algo.startswith("gram") else a_res.iters + 1
@@ -973,13 +1019,14 @@ def main():
 
     # full-size correctness: the fp64 fixed-point step at the returned aggregate
     check = None
-    if not args.no_check and agg_name == "gm2":
+    do_check = args.full and not args.no_check
+    if do_check and agg_name == "gm2":
         step, gn = fixed_point_step(src, out, allreduce)
         check = {"what": "fp64 gm2 step ||T(g) - g|| at the returned g over the full K x d "
                          "(T = M:174-179); the reference stops at movement <= tol = 1e-5",
                  "fixed_point_step": step, "g_norm": gn, "relative": step / max(gn, 1e-300),
                  "last_movement": res.last_movement, "ok": step <= 1e-4}
-    elif not args.no_check:
+    elif do_check:
         check = {"what": "gm (AirComp) never converges (fresh channel draw each iteration, "
                          "SURVEY §3C); parity is pinned by tests/test_gpu_weiszfeld.py",
                  "iters": res.iters, "finite": bool(torch.isfinite(out).all())}
@@ -1102,7 +1149,7 @@ def main():
             "alt_layout": alt,
             "soak": soak,
         }
-        if world == 1 and not args.no_cpu and not args.rehearse_shard:
+        if args.full and world == 1 and not args.no_cpu and not args.rehearse_shard:
             line["cpu_baseline"] = cpu_baseline(src, g0, agg_name, var, res.iters, d_total,
                                                 args.cpu_budget, args.cpu_d)
         print(json.dumps(line), file=json_out, flush=True)

@@ -30,9 +30,16 @@ def golden_manifest():
 
 
 def golden_case(name):
+    """(manifest entry, arrays) of a fixture.  A fixture too large for one committed file
+    (1 MiB) continues in the entry's `more_files`: each holds the next rows of the arrays
+    it names, appended along axis 0 (tests/golden/make_golden.py writes them)."""
     for c in golden_manifest()["cases"]:
         if c["name"] == name:
-            return c, dict(np.load(os.path.join(GOLDEN, c["file"])))
+            arr = dict(np.load(os.path.join(GOLDEN, c["file"])))
+            for more in c.get("more_files", []):
+                for k, v in np.load(os.path.join(GOLDEN, more)).items():
+                    arr[k] = np.concatenate([arr[k], v], axis=0)
+            return c, arr
     raise KeyError(name)
 
 

@@ -42,8 +42,8 @@ def test_bench_two_ranks_c3_small():
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-gpu",
-                        "--workload", "c3-small", "--steps", "2", "--warmup", "1", "--no-cpu",
-                        "--soak", "0", "--alt-steps", "0"],
+                        "--workload", "c3-small", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu", "--soak", "0", "--alt-steps", "0"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -58,6 +58,47 @@ def test_bench_two_ranks_c3_small():
     assert cfg["iters"] == want_iters, (cfg["iters"], want_iters)
 
 
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_the_last_steps_aggregate(tmp_path):
+    """A plain one-GPU run (no --full) on the 50 x 100k problem: --steps timed steps, the legs
+    behind --full absent from the line, and --dump-outputs holding what gm2 returns for the
+    bench's seeded input.  Bar: the same kernels on the same data, so only the order of the
+    fp32 partial sums may differ between the two processes — rel L2 <= 1e-6 (~16 ulp)."""
+    import numpy as np
+    import byzantine_aircomp_amd as bz
+    K, d, B = 50, 100_000, 10
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--workload", "c5-problem", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=250)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for leg in ("check", "cpu_baseline", "alt_layout", "soak"):
+        assert line[leg] is None, (leg, line[leg])
+    got = np.load(tmp_path / "aggregate.npy")
+    assert got.dtype == np.float32 and got.shape == (d,)
+    ctx = bz.context()
+    s = torch.cuda.current_stream().cuda_stream
+    X = torch.empty(K, d, device="cuda")
+    bz._lib.check(ctx.lib.gm_fill_clients_f32(ctx.handle, X.data_ptr(), K, d, d, B, 0.0, 0.05,
+                                              0.25, 0.5, 20211, s), "fill")
+    g0 = torch.empty(d, device="cuda")
+    bz._lib.check(ctx.lib.gm_fill_normal_f32(ctx.handle, g0.data_ptr(), d, 0.0, 0.01, 20212, s),
+                  "fill")
+    want = bz.gm2(X, {"maxiter": 1000, "tol": 1e-5, "guess": g0}).cpu().numpy()
+    iters = bz.aggregators.last_result.iters
+    rel = float(np.linalg.norm(got.astype(np.float64) - want) / np.linalg.norm(want))
+    print("rel", rel, "iters", iters, np.load(tmp_path / "iters.npy"))
+    assert rel <= 1e-6, rel
+    assert abs(float(np.load(tmp_path / "iters.npy")[0]) - iters) <= 1
+
+
 @pytest.mark.timeout(600)
 def test_bench_two_ranks_c5_sweep():
     """The C5 sweep through the launcher at N = 2: each rank takes its contiguous share of
@@ -66,7 +107,7 @@ def test_bench_two_ranks_c5_sweep():
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-gpu",
                         "--workload", "c5", "--problems", "32", "--steps", "1", "--warmup", "1",
-                        "--no-cpu", "--soak", "0", "--alt-steps", "0"],
+                        "--full", "--no-cpu", "--soak", "0", "--alt-steps", "0"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

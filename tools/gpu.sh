@@ -8,7 +8,8 @@
 # fault, an abort or a timeout).  STEP forms:
 #   suite[:PYTEST_ARGS]       pytest -m gpu (all tests, or the given files / -k args)
 #   smoke                     __graft_entry__.smoke()
-#   bench:NAME[:ARGS]         python bench.py ARGS  -> NAME.json / NAME.err
+#   bench:NAME[:ARGS]         python bench.py ARGS  -> NAME.json / NAME.err  (--full in ARGS:
+#                             CPU baseline, check, other layout and soak as well)
 #   trace:NAME[:ARGS]         rocprofv3 --kernel-trace --stats of bench.py ARGS -> NAME/
 #   pmc:NAME:COUNTER[:ARGS]   one rocprofv3 --pmc pass (one counter) of bench.py ARGS
 #   py:NAME:SCRIPT[:ARGS]     python SCRIPT ARGS -> NAME.log (tools/*.py probes)

@@ -16,11 +16,11 @@ B_FAST="--no-cpu --alt-steps 0 --soak 0"
 closing() {
   # GPU suite + smoke + the default bench line (tools/final_check.sh), every BASELINE
   # workload's line, C2's kernel trace and the f3 timings (DESIGN.md §4's table)
-  bash tools/final_check.sh || return $?
+  bash tools/final_check.sh $O/final || return $?
   for w in "c2:--workload c2" "c5:--workload c5" "c5air:--workload c5 --reading aircomp" \
            "c4:--workload c4 --steps 5 --warmup 1" "c4shard:--workload c4-shard"; do
     n=${w%%:*}; a=${w#*:}
-    timeout -k 10 600 python -u bench.py $a > $O/bench_$n.json 2> $O/bench_$n.err || { tail -20 $O/bench_$n.err; return 2; }
+    timeout -k 10 600 python -u bench.py --full $a > $O/bench_$n.json 2> $O/bench_$n.err || { tail -20 $O/bench_$n.err; return 2; }
     cut -c1-300 $O/bench_$n.json
   done
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_c2 -o t -- \

@@ -13,7 +13,7 @@ if [ "$2" != "skip-tests" ]; then
     > "$out/pytest_gpu.log" 2>&1
   rc=$?; tail -3 "$out/pytest_gpu.log"; [ $rc -gt 1 ] && exit $rc
 fi
-timeout -k 10 600 python bench.py > "$out/bench.json" 2> "$out/bench.err" || exit 3
+timeout -k 10 600 python bench.py --full > "$out/bench.json" 2> "$out/bench.err" || exit 3
 tail -1 "$out/bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o c3 -- \
   python bench.py --steps 5 --warmup 1 --no-cpu --alt-steps 0 > "$out/trace.log" 2>&1 || exit 4
