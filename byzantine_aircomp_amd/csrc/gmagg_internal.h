@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (api.hip) and the kernels.
+// Internal interface between the C-ABI layer (api.hip, host_*.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +17,7 @@ struct alignas(64) KState {
   double last_movement;  // fp32 movement of the last body, widened
   float a_noise;         // scale of the per-column noise in the next pass (AIRCOMP)
   float s;               // scaler sqrt(mean(g^2)) of the current iterate (AIRCOMP)
-  // Gram variant, written by gram_solve for the AUTO accuracy guard (api.hip):
+  // Gram variant, written by gram_solve for the AUTO accuracy guard (host_weiszfeld.hip):
   double guard_q;        // ||X'^T b||: one-step error of the K-space map (gram_verify)
   double guard_r;        // last / previous K-space movement (contraction estimate)
   int32_t gram_bad;      // the reduced Gram has a non-finite entry (f16 overflow or input)

@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(256) gram_partial(const float* __restrict__ X,
 // enough: for rows that nearly coincide the m parts are coherent and mm^T is a
 // 2^-16-relative bias on D (measured: 2.5e-4 relative error on a tight
 // cluster).  What is left — the bits of x' beyond h + m (<= 2^-17 |x'|) and fp32
-// accumulation — is priced at run time by the AUTO guard (api.hip, run_gram).
+// accumulation — is priced at run time by the AUTO guard (host_weiszfeld.hip, run_gram).
 //
 // Block: 256 threads; stage = 64 columns x KP rows, loaded as float4 by all
 // threads (16 B per row segment, 16 rows per wave instruction), centred, split
@@ -387,7 +387,7 @@ __global__ void __launch_bounds__(512, 1) gram_split_partial(const float* __rest
 // smaller ones keep an absolute precision of 2^-24 (f16 subnormals, which the
 // f16 MFMA and conversion keep), i.e. 2^-27 of the row's largest element.  An
 // element beyond the headroom becomes inf, G non-finite: gram_check flags it
-// (KState::gram_bad) and the host reruns the bf16 split (api.hip run_gram).
+// (KState::gram_bad) and the host reruns the bf16 split (host_weiszfeld.hip run_gram).
 //
 // Block = 4 waves, ONE per SIMD with the whole 512-entry register file, and no
 // producer/consumer split: every wave streams a quarter of each 64-column stage
@@ -1075,7 +1075,7 @@ __global__ void __launch_bounds__(1024) gram_solve(const double* __restrict__ G,
   }
 }
 
-// A posteriori check of the Gram path (AUTO guard, api.hip run_gram).  The
+// A posteriori check of the Gram path (AUTO guard, host_weiszfeld.hip run_gram).  The
 // closing pass was a full streaming STEP pass at the returned weights a, so
 // `Dx` holds the exact ||x_k - g||^2 (fp32 elements, fp64 sums, as the
 // streaming path computes them).  Compare the next Weiszfeld weights from the

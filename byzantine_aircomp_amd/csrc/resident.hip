@@ -260,7 +260,7 @@ __host__ __device__ constexpr int64_t res_values(int64_t K) { return 2 * K + 2; 
 
 // EXCH (the exchange, a template parameter so that each variant carries only its own code:
 // C2's one-XCD kernel is the round-4 instruction stream): 0 flat (agent-scope, or L2-kept on
-// one XCD), 1 the XCD-hierarchical gather, 2 the split-scope exchange (api.hip chooses)
+// one XCD), 1 the XCD-hierarchical gather, 2 the split-scope exchange (host_weiszfeld.hip run_resident chooses)
 template <int V, int NW, int LPR, int R, int CPB, int EXCH = 0>
 __global__ void __launch_bounds__(NW * 64) weiszfeld_resident(ResArgs a) {
   constexpr int QW = 64 / LPR;
@@ -861,7 +861,7 @@ static const void* resident_kernel(const PassCfg& cfg, int cpb, int xg = 0) {
 // Blocks of CPB chunks each: the smallest CPB (up to 8) that brings the grid to at most
 // kResTargetBlocks blocks, or the largest valid one; GMAGG_RES_CPB=n forces
 // n (A/B).  Returns false when the grid cannot be co-resident.
-constexpr int kResTargetBlocks = 32;   // one XCD's CUs (the L2-kept exchange, api.hip)
+constexpr int kResTargetBlocks = 32;   // one XCD's CUs (the L2-kept exchange, host_weiszfeld.hip)
 
 bool resident_plan(const PassCfg& cfg, int64_t nch, int num_cu, int* cpb_out, int* nb_out) {
   int cpb = 0;

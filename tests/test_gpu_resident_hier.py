@@ -141,6 +141,27 @@ def test_hier_checkin_failure_streams(monkeypatch):
     bz.aggregators.close_all()
 
 
+def test_checkin_failure_is_not_timed_as_a_pass(monkeypatch):
+    """Pass timing over a call whose resident grid fails its check-in and streams: the
+    failed resident launch's event pair is given back, so the timed launches are the
+    streaming STEP passes, one per iteration."""
+    import byzantine_aircomp_amd as bz
+    bz.aggregators.close_all()                       # a fresh context (no skip state)
+    X, p = _caller(50, 2048, 6)
+    Xd, opts = X.cuda(), {"maxiter": 1000, "tol": 1e-5, "guess": p.cuda()}
+    monkeypatch.setenv("GMAGG_RES_CHECKIN_FAIL", "1")
+    ctx = bz.context()
+    ctx.pass_timing(True)
+    bz.gm2(Xd, dict(opts))
+    torch.cuda.synchronize()
+    _, launches = ctx.pass_timing(False)
+    monkeypatch.delenv("GMAGG_RES_CHECKIN_FAIL")
+    res = bz.aggregators.last_result
+    bz.aggregators.close_all()                       # (the skip window goes with the context)
+    assert res.algo == "stream", res
+    assert launches == res.iters, (launches, res)
+
+
 def iteration_cases():
     """The +-1 inputs above, for tests/test_iteration_wellposed.py."""
     cases = []

@@ -195,7 +195,7 @@ def test_gm_philox_reproducible_and_close_to_ideal():
                                              (50, 1 << 22, 0, False), (1000, 65537, 0, False)])
 def test_gm_rows_staged_as_panels(K, d, pad, exact):
     """Row-major AirComp gm with >= 64 passes on K*d >= 2^24 packs a panel copy once and
-    streams every pass from it (api.hip gm_weiszfeld_f32).  Against the row-major passes
+    streams every pass from it (host_weiszfeld.hip gm_weiszfeld_f32).  Against the row-major passes
     (algo="stream"): bit-identical where both run the same tile (K=300, d % 4 == 0),
     relative L2 1e-5 otherwise (K=50: another tile; d odd: float1 rows); the same
     iteration count (gm runs to maxiter).  Sizes beyond the register-resident kernel;
@@ -277,6 +277,33 @@ def test_gm2_translation_and_permutation_invariance():
     assert rel_l2(moved.cpu().numpy(), base.cpu().numpy()) < 1e-5
     shift = bz().gm2(X + 1.0, {"maxiter": 100, "tol": 1e-6})
     assert rel_l2((shift - 1.0).cpu().numpy(), base.cpu().numpy()) < 1e-4
+
+
+def test_stream_lagged_poll_times_one_launch_per_iteration():
+    """check_every=1 polls with a lag of one iteration, so one pass is queued past the stop
+    and exits at once: its timing pair is dropped (launches == iterations), and the
+    aggregate and the count are the oracle's."""
+    m = bz()
+    K, d = 1000, 4096
+    ctx = m.context()
+    s = torch.cuda.current_stream().cuda_stream
+    X = torch.empty(K, d, device="cuda")
+    m._lib.check(ctx.lib.gm_fill_clients_f32(ctx.handle, X.data_ptr(), K, d, d, 200, 0.0, 0.05,
+                                             0.25, 0.5, 20211, s), "fill")
+    g0 = torch.empty(d, device="cuda")
+    m._lib.check(ctx.lib.gm_fill_normal_f32(ctx.handle, g0.data_ptr(), d, 0.0, 0.01, 20212, s),
+                 "fill")
+    torch.cuda.synchronize()
+    opts = {"maxiter": 1000, "tol": 1e-5}
+    want, tr = orc.gm2(X.cpu(), dict(opts, guess=g0.cpu()))
+    ctx.pass_timing(True)
+    got = m.gm2(X, dict(opts, guess=g0, algo="stream", check_every=1))
+    torch.cuda.synchronize()
+    _, launches = ctx.pass_timing(False)
+    res = m.aggregators.last_result
+    assert res.algo == "stream" and launches == res.iters, (res, launches)
+    assert rel_l2(got.cpu().numpy(), want.numpy()) <= TOL
+    assert abs(res.iters - tr.iters) <= ITER_SLACK, (res, tr)
 
 
 def test_gm2_large_fixed_point_property():
@@ -556,6 +583,44 @@ def test_pre_oma_equals_oma_then_gm2(K, d, layout, algo):
     assert torch.equal(da, db)
     assert torch.equal(a, b)
     assert (ra.iters, ra.algo) == (rb.iters, rb.algo)
+
+
+@pytest.mark.parametrize("layout", ["rows", "panels"])
+def test_c_abi_maxiter_zero_applies_pre_oma_and_returns_guess(layout):
+    """gm_weiszfeld_f32 with maxiter == 0 (the drop-in module answers that case itself, so
+    the C ABI's branch is called directly): out is the guess, as oracle.gm2 returns it
+    (M:173, M:184), and pre_oma still noises X exactly as OMA does."""
+    import ctypes as C
+
+    import byzantine_aircomp_amd as bz
+    from byzantine_aircomp_amd import _lib
+    K, d = 12, 1030
+    g = torch.Generator().manual_seed(K + d)
+    X = (0.05 * torch.randn(K, d, generator=g)).cuda()
+    g0 = (0.01 * torch.randn(d, generator=g)).cuda()
+
+    def fresh():
+        return bz.ClientPanels.from_rows(X) if layout == "panels" else X.clone()
+
+    A = fresh()
+    bz.OMA(A, 1e-2, seed=77)
+    B = fresh()
+    ptr, ldx = (B.data.data_ptr(), B.panel_stride) if layout == "panels" else (B.data_ptr(), d)
+    o = _lib.GmOpts()
+    o.maxiter, o.tol, o.eps = 0, 1e-5, 1e-4
+    o.layout = _lib.GM_LAYOUT_PANELS if layout == "panels" else _lib.GM_LAYOUT_ROWS
+    o.pre_oma, o.pre_oma_var, o.pre_oma_seed = 1, 1e-2, 77
+    out = torch.full((d,), float("nan"), device="cuda")
+    rr = _lib.GmResult()
+    ctx = bz.context()
+    _lib.check(ctx.lib.gm_weiszfeld_f32(ctx.handle, ptr, K, d, ldx, g0.data_ptr(), out.data_ptr(),
+                                        C.byref(o), C.byref(rr),
+                                        torch.cuda.current_stream().cuda_stream), "maxiter 0")
+    torch.cuda.synchronize()
+    want, tr = orc.gm2(X.cpu(), {"maxiter": 0, "tol": 1e-5, "guess": g0.cpu()})
+    assert torch.equal(out.cpu(), want) and rr.iters == tr.iters == 0
+    da, db, clean = ((t.data if layout == "panels" else t) for t in (A, B, fresh()))
+    assert torch.equal(da, db) and not torch.equal(db, clean)
 
 
 @pytest.mark.parametrize("layout,d", [("rows", 10000), ("panels", 10000), ("rows", 1001),

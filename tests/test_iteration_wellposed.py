@@ -71,8 +71,8 @@ def test_iteration_count_well_posed(thunk):
 
 def test_floor_constant_shared_with_the_gram_guard():
     """The count window and the Gram guard's floor rule use ONE floor:
-    oracle FLOOR_ULPS == gmagg_internal.h kFloorUlps (read from the source), and api.hip's
-    guard computes its floor from that constant."""
+    oracle FLOOR_ULPS == gmagg_internal.h kFloorUlps (read from the source), and run_gram's
+    guard (host_weiszfeld.hip) computes its floor from that constant."""
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,8 +80,8 @@ def test_floor_constant_shared_with_the_gram_guard():
     hdr = open(os.path.join(csrc, "gmagg_internal.h")).read()
     m = re.search(r"constexpr double kFloorUlps = ([0-9.]+);", hdr)
     assert m and float(m.group(1)) == orc.FLOOR_ULPS
-    api = open(os.path.join(csrc, "api.hip")).read()
-    assert "const double floor = kFloorUlps * u * gn;" in api
+    host = open(os.path.join(csrc, "host_weiszfeld.hip")).read()
+    assert "const double floor = kFloorUlps * u * gn;" in host
 
 
 def test_assert_iter_count_bites():
