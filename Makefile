@@ -8,7 +8,7 @@ BUILD    := build/obj
 LIB      := byzantine_aircomp_amd/libgmagg.so
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-result \
             -I include -munsafe-fp-atomics
-SRCS     := $(CSRC)/stream_pass.hip $(CSRC)/gram.hip $(CSRC)/resident.hip $(CSRC)/resident_batched.hip $(CSRC)/coordinate.hip $(CSRC)/weiszfeld.hip $(CSRC)/oma.hip $(CSRC)/pack.hip $(CSRC)/clients.hip $(CSRC)/api.hip $(CSRC)/rows_pass.hip $(CSRC)/host_weiszfeld.hip $(CSRC)/host_batched.hip
+SRCS     := $(CSRC)/stream_pass.hip $(CSRC)/gram.hip $(CSRC)/resident.hip $(CSRC)/resident_batched.hip $(CSRC)/coordinate.hip $(CSRC)/weiszfeld.hip $(CSRC)/oma.hip $(CSRC)/pack.hip $(CSRC)/clients.hip $(CSRC)/api.hip $(CSRC)/rows_pass.hip $(CSRC)/host_weiszfeld.hip $(CSRC)/host_batched.hip $(CSRC)/stream_pass_bf16.hip
 OBJS     := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/gmagg.h
 
@@ -18,6 +18,10 @@ all: $(LIB)
 # scalar v_fma_f32 instead of v_pk_fma_f32, which the MFMA waves sharing its SIMD pay
 # for (C4 shard Gram partial 3.30 -> 2.97 ms; profiles/history/r2_gram_producer_ab.txt)
 $(BUILD)/gram.o: HIPFLAGS += -fno-slp-vectorize
+# stream_pass_bf16.hip likewise: its arithmetic is written on column pairs already, and the
+# vectorizer's further pairings only cost registers (K <= 1024 STEP kernel 125 vs 121 VGPRs;
+# before the pair form, 96 bytes of scratch per lane vs none)
+$(BUILD)/stream_pass_bf16.o: HIPFLAGS += -fno-slp-vectorize
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -45,6 +49,7 @@ ALT_SEL   := $(if $(ALT_ONLY),$(foreach n,$(ALT_ONLY),$(CSRC)/$(n).hip),$(SRCS))
 ALT_OBJS  := $(patsubst $(CSRC)/%.hip,$(BUILD)/alt/%.o,$(ALT_SEL)) \
              $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(filter-out $(ALT_SEL),$(SRCS)))
 $(BUILD)/alt/gram.o: HIPFLAGS += -fno-slp-vectorize
+$(BUILD)/alt/stream_pass_bf16.o: HIPFLAGS += -fno-slp-vectorize
 $(BUILD)/alt/%.o: $(CSRC)/%.hip $(HDRS) FORCE
 	@mkdir -p $(BUILD)/alt
 	$(HIPCC) $(HIPFLAGS) $(ALT_FLAGS) -c $< -o $@

@@ -12,7 +12,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GMAGG_LIB") or os.path.join(HERE, "libgmagg.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 GM_MODE_IDEAL, GM_MODE_AIRCOMP = 0, 1
 GM_NOISE_PHILOX, GM_NOISE_HOST = 0, 1
@@ -75,6 +75,9 @@ SIGNATURES = [
     ("gm_weiszfeld_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, C.POINTER(GmOpts),
                                    C.POINTER(GmResult), _P]),
     ("gm_panel_width", _I64, [_I64]),
+    ("gm_weiszfeld_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, C.POINTER(GmOpts),
+                                    C.POINTER(GmResult), _P]),
+    ("gm_panel_width_bf16", _I64, [_I64]),
     ("gm_weiszfeld_batched_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
                                            _I64, C.POINTER(GmOpts), C.POINTER(GmResult), _P]),
     ("gm_mean_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
@@ -96,6 +99,8 @@ SIGNATURES = [
     ("gm_oma_philox_batched_panels_f32", C.c_int,
      [_P, _P, _I64, _I64, _I64, _I64, _I64, C.c_double, C.c_uint64, _P]),
     ("gm_rows_to_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _I64, _I64, _P]),
+    ("gm_rows_to_panels_bf16_from_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _I64, _I64, _P]),
+    ("gm_rows_to_panels_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _I64, _I64, _P]),
     ("gm_oma_apply_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     ("gm_client_chain_f32", C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64,
                                       C.c_int32, C.c_float, C.c_float, _P, _P, _P, _I64,

@@ -28,8 +28,11 @@ comparison), ``seed`` (Philox key; drawn from the torch CPU generator when
 absent) and ``algo`` (``"auto"``, ``"stream"``, ``"twopass"``, ``"gram"``,
 ``"gram_f32"``, ``"resident"``).  ``gm2`` / ``gm`` also accept a
 ``ClientPanels`` (panels.py: the same K x d values in the panel layout the
-streaming pass reads as contiguous blocks) in place of the ``[K, d]`` tensor.  The trace of
-the last call (iterations, last movement) is in ``last_result``.
+streaming pass reads as contiguous blocks) in place of the ``[K, d]`` tensor, and client
+updates stored as bf16 (a ``torch.bfloat16`` ``[K, d]`` tensor or bf16 ``ClientPanels``):
+the fused streaming pass reads them widened to fp32, which is exact, at half the bytes per
+pass; guess, iterates and result are fp32.  The other aggregators are fp32 only.  The trace
+of the last call (iterations, last movement) is in ``last_result``.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -173,9 +176,9 @@ def _stream_ptr(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def _stage(t: torch.Tensor) -> torch.Tensor:
+def _stage(t: torch.Tensor, bf16_ok: bool = False) -> torch.Tensor:
     """The GPU tensor the kernels read (a copy if `t` lives on the CPU)."""
-    if t.dtype != torch.float32:
+    if t.dtype != torch.float32 and not (bf16_ok and t.dtype == torch.bfloat16):
         raise TypeError(f"aggregation kernels are fp32 (got {t.dtype})")
     if t.device.type == "cuda":
         return t
@@ -189,6 +192,26 @@ def _rows(X: torch.Tensor):
     if X.stride(1) != 1 or X.stride(0) < X.shape[1] or X.shape[0] == 0:
         X = X.contiguous()
     return X, max(X.stride(0), X.shape[1])
+
+
+def _fp32_panels(p: ClientPanels, who: str) -> ClientPanels:
+    if p.dtype != torch.float32:
+        raise TypeError(f"{who} is fp32 only (got {p.dtype} ClientPanels); gm2 / gm read bf16")
+    return p
+
+
+def _bf16_operand(X: torch.Tensor):
+    """(tensor, ldx, layout) of a bf16 [K, d] CUDA matrix for gm_weiszfeld_bf16: the rows
+    themselves where the kernel can read them (unit column stride, 16-byte aligned, d and the
+    row stride multiples of 8), else a packed copy in bf16 panels.  X is never written."""
+    if X.dim() != 2:
+        raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
+    K, d = X.shape
+    if (K > 0 and X.stride(1) == 1 and X.stride(0) >= d and X.stride(0) % 8 == 0 and d % 8 == 0
+            and X.data_ptr() % 16 == 0):
+        return X, X.stride(0), _lib.GM_LAYOUT_ROWS
+    P = ClientPanels.from_rows(X)
+    return P.data, P.panel_stride, _lib.GM_LAYOUT_PANELS
 
 
 def _noise_source(options) -> int:
@@ -243,8 +266,11 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
         OMA(wList, float(pre_var), noise_source=opts.get("noise_source"), seed=pre_seed)
         pre_var = None
     guess = opts.get("guess")
+    bf16 = wList.dtype == torch.bfloat16
     if guess is None:
-        guess = wList.mean(dim=0)
+        # (bf16 rows: the fp32 mean of the widened values, no widened copy of the matrix)
+        guess = wList.mean(dim=0, dtype=torch.float32) if bf16 and not isinstance(
+            wList, ClientPanels) else wList.mean(dim=0)
     maxiter = int(opts["maxiter"])
     if maxiter <= 0:                        # M:145 / M:173 loop body never runs
         if pre_var is not None:
@@ -255,6 +281,9 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
     if isinstance(wList, ClientPanels):
         X, ldx, layout = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
         K, d = wList.shape
+    elif bf16:
+        K, d = wList.shape
+        X, ldx, layout = _bf16_operand(_stage(wList, bf16_ok=True))
     else:
         X = _stage(wList)
         X, ldx = _rows(X)
@@ -293,10 +322,11 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
             o.seed = _seed(opts)
     ctx = context(X.device)
     res = _lib.GmResult()
+    fn = "gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32"
     with torch.cuda.device(X.device):
-        _lib.check(ctx.lib.gm_weiszfeld_f32(ctx.handle, X.data_ptr(), K, d, ldx, g0.data_ptr(),
-                                            out.data_ptr(), C.byref(o), C.byref(res),
-                                            _stream_ptr(X.device)), "gm_weiszfeld_f32")
+        _lib.check(getattr(ctx.lib, fn)(ctx.handle, X.data_ptr(), K, d, ldx, g0.data_ptr(),
+                                        out.data_ptr(), C.byref(o), C.byref(res),
+                                        _stream_ptr(X.device)), fn)
     last_result = _result(res)
     if pre_var is not None and not isinstance(wList, ClientPanels) and X is not wList:
         # a strided view was packed into a copy: the fused pre-noise landed in the
@@ -306,17 +336,20 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
 
 
 def gm2(wList, options={}):  # noqa: B006 - the reference's signature (M:162)
-    """Ideal Weiszfeld geometric median (MNIST_Air_weight.py:162-184)."""
+    """Ideal Weiszfeld geometric median (MNIST_Air_weight.py:162-184).  fp32 or bf16 client
+    updates; the result is fp32 either way."""
     return _weiszfeld(wList, options, aircomp=False)
 
 
 def gm(wList, options={}):  # noqa: B006 - the reference's signature (M:131)
-    """AirComp Weiszfeld geometric median (MNIST_Air_weight.py:131-160)."""
+    """AirComp Weiszfeld geometric median (MNIST_Air_weight.py:131-160).  fp32 or bf16 client
+    updates; the result is fp32 either way."""
     return _weiszfeld(wList, options, aircomp=True)
 
 
 def _coordinate(wList, fn_name, *extra):
     if isinstance(wList, ClientPanels):          # the *_panels_f32 kernels (same results)
+        _fp32_panels(wList, fn_name[3:-4])
         X, ldx, fn_name = wList.data, wList.panel_stride, fn_name.replace("_f32", "_panels_f32")
         K, d = wList.shape
         out = torch.empty(d, dtype=torch.float32, device=X.device)
@@ -355,6 +388,7 @@ def Krum(wList, options):  # noqa: N802 - reference name (M:197)
     """The row with the smallest sum of squared distances to its honestSize-1
     nearest rows, itself included (M:197-204)."""
     if isinstance(wList, ClientPanels):
+        _fp32_panels(wList, "Krum")
         X, ldx, fn = wList.data, wList.panel_stride, "gm_krum_panels_f32"
         K, d = wList.shape
     else:
@@ -383,6 +417,7 @@ def honest_variance(w_local, honestSize: int) -> torch.Tensor:
     of ||x_k - mean||^2, one streaming pass (fp64 sums); a 0-dim fp32 tensor."""
     out = torch.empty((), dtype=torch.float32, device=w_local.device)
     if isinstance(w_local, ClientPanels):
+        _fp32_panels(w_local, "honest_variance")
         ctx = context(w_local.device)
         with torch.cuda.device(w_local.device):
             _lib.check(ctx.lib.gm_honest_variance_panels_f32(
@@ -407,6 +442,7 @@ def honest_variance(w_local, honestSize: int) -> torch.Tensor:
 def OMA(message, noise_var=0.01, noise_source=None, seed=None):  # noqa: N802 - reference name
     """In-place per-client equalised AWGN (MNIST_Air_weight.py:385-394)."""
     if isinstance(message, ClientPanels):
+        _fp32_panels(message, "OMA")
         src = _noise_source({} if noise_source is None else {"noise_source": noise_source})
         if src == _lib.GM_NOISE_HOST:          # the reference's [K, d] draws: via rows
             rows = message.to_rows()

@@ -18,6 +18,11 @@ int64_t gm_panel_width(int64_t K) {
   return K >= 1 && pick_cfg(K, 4, 1, &cfg, true) ? (int64_t)cfg.LPR * cfg.V : 0;
 }
 
+int64_t gm_panel_width_bf16(int64_t K) {
+  PassCfg cfg{};
+  return K >= 1 && pick_cfg(K, 8, 1, &cfg, true, true) ? (int64_t)cfg.LPR * cfg.V : 0;
+}
+
 int gm_ctx_create(int device, gm_ctx** out) {
   if (!out) return fail(GM_ERR_INVALID, "gm_ctx_create: out is NULL");
   *out = nullptr;
@@ -437,6 +442,28 @@ int gm_rows_to_panels_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64
   HIPCHK(launch_rows_to_panels(X, K, d, ldx, P, W, panel_stride,
                                reinterpret_cast<hipStream_t>(stream)));
   return GM_OK;
+}
+
+static int pack_bf16(gm_ctx* c, const void* X, bool src_f32, int64_t K, int64_t d, int64_t ldx,
+                     uint16_t* P, int64_t W, int64_t panel_stride, void* stream, const char* who) {
+  if (!c || !X || !P || K < 0 || d < 0 || ldx < d || W < 1 || panel_stride < K * W)
+    return fail(GM_ERR_INVALID, "%s: bad args", who);
+  if (K == 0 || d == 0) return GM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(launch_rows_to_panels_bf16(X, src_f32, K, d, ldx, P, W, panel_stride,
+                                    reinterpret_cast<hipStream_t>(stream)));
+  return GM_OK;
+}
+
+int gm_rows_to_panels_bf16_from_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
+                                    uint16_t* P, int64_t W, int64_t panel_stride, void* stream) {
+  return pack_bf16(c, X, true, K, d, ldx, P, W, panel_stride, stream,
+                   "gm_rows_to_panels_bf16_from_f32");
+}
+
+int gm_rows_to_panels_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                           uint16_t* P, int64_t W, int64_t panel_stride, void* stream) {
+  return pack_bf16(c, X, false, K, d, ldx, P, W, panel_stride, stream, "gm_rows_to_panels_bf16");
 }
 
 int gm_client_chain_f32(gm_ctx* c, const float* data, int64_t ldd, const int64_t* labels,

@@ -24,6 +24,15 @@ __device__ __forceinline__ void load_cols(const float* __restrict__ p, float (&o
     for (int i = 0; i < V; ++i) o[i] = v[i];
   }
 }
+// The same 16 bytes as four 32-bit words (a lane's 8 packed bf16 columns).
+template <int V>
+__device__ __forceinline__ void load_cols(const uint32_t* __restrict__ p, uint32_t (&o)[V]) {
+  static_assert(V == 4, "packed rows are read 16 bytes at a time");
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = v[i];
+}
 
 // V consecutive floats at byte offset `off` from the wave-uniform `base`, through
 // a raw buffer resource (offsets >= nrec read 0),
@@ -47,6 +56,18 @@ __device__ __forceinline__ void load_rows(const float* base, uint32_t off, float
   } else {
     o[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 2));
   }
+}
+
+template <int V>
+__device__ __forceinline__ void load_rows(const uint32_t* base, uint32_t off, uint32_t (&o)[V],
+                                          int nrec = 0x7fffffff) {
+  static_assert(V == 4, "packed rows are read 16 bytes at a time");
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(base), 0, nrec, 0x00020000);
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  const u4 v = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = v[i];
 }
 
 template <int A, int B> struct cmin { static constexpr int v = A < B ? A : B; };

@@ -31,10 +31,14 @@ struct alignas(64) KState {
 struct PassCfg {
   int V, NW, LPR, R;
   int OCC = 1;   // blocks per CU the kernel's registers are capped for
+  // X holds bf16 elements (gm_weiszfeld_bf16): V = 8 columns per lane, one 16-byte load as
+  // the fp32 tile's V = 4, so the bytes per row segment, per chunk and per load and the
+  // register tile are the fp32 tile's and the chunk is twice as wide (J = LPR * 8)
+  bool B16 = false;
 };
 
 struct PassArgs {
-  const float* X;
+  const float* X;         // bf16 tiles (PassCfg.B16): uint16_t elements behind the same pointer
   int64_t K, d, ldx;
   const float* g_old;     // iterate t (INIT: the initial guess)
   float* g_new;           // iterate t+1 (STEP)
@@ -115,6 +119,10 @@ int pass_blocks_per_cu(const PassCfg& cfg, int mode);
 bool rows_pass_eligible(const PassArgs& a, int mode);
 hipError_t launch_rows_pass(int mode, int grid, const PassArgs& a, hipStream_t s);
 bool pass_cfg_supported(const PassCfg& cfg);
+int pass_variant();   // GMAGG_PASS_VARIANT (stream_pass.hip), -1 unset
+// The bf16-input instantiations (stream_pass_bf16.hip): the tiles pick_cfg returns, modes
+// 0-2, both layouts, the plain and the rolling schedule; nullptr for anything else.
+const void* pass_kernel_bf16(const PassCfg& cfg, int mode, bool panel);
 
 // Reduction, K-space step and the two-pass path (weiszfeld.hip).
 hipError_t launch_slab_reduce(const double* slab, int nb, int64_t S, double* sums,
@@ -314,6 +322,11 @@ hipError_t launch_oma_apply(float* X, int64_t K, int64_t d, int64_t ldx, const f
                             const float* hi, const float* nr, const float* ni, hipStream_t s);
 hipError_t launch_rows_to_panels(const float* X, int64_t K, int64_t d, int64_t ldx, float* P,
                                  int64_t W, int64_t pstride, hipStream_t s);
+// bf16 panels from row-major fp32 (round to nearest even, as torch's .to(bfloat16)) or
+// bf16 rows (pack.hip)
+hipError_t launch_rows_to_panels_bf16(const void* X, bool src_f32, int64_t K, int64_t d,
+                                      int64_t ldx, uint16_t* P, int64_t W, int64_t pstride,
+                                      hipStream_t s);
 hipError_t launch_oma_philox(float* X, int64_t K, int64_t d, int64_t ldx, int64_t d_total,
                              int64_t col_off, float sd, uint64_t seed, hipStream_t s,
                              int wshift = 0, int64_t problems = 1, int64_t pstride = 0);

@@ -1,5 +1,5 @@
 // Host-only internals of the C-ABI layer, shared by api.hip (context API, thin wrappers,
-// Krum), host_weiszfeld.hip (gm_weiszfeld_f32) and host_batched.hip
+// Krum), host_weiszfeld.hip (gm_weiszfeld_f32, gm_weiszfeld_bf16) and host_batched.hip
 // (gm_weiszfeld_batched_f32): the context, error reporting, workspace and pinned-buffer
 // helpers, the all-reduce, pass timing, tile choices and the environment knobs.
 #pragma once
@@ -401,7 +401,9 @@ inline void drop_last_timing(gm_ctx* c) {
 // R rows each cover K.  Bigger K -> narrower chunk, so a block's tile (and the
 // bytes it has in flight) stays ~64-128 KiB.
 // panel: the tile of a panel-layout call (its chunk width is the panel width W).
-inline bool pick_cfg(int64_t K, int V, int64_t ldx, PassCfg* cfg, bool panel = false) {
+// b16: the same tile on bf16 elements (V = 8; PassCfg.B16).
+inline bool pick_cfg(int64_t K, int V, int64_t ldx, PassCfg* cfg, bool panel = false,
+                     bool b16 = false) {
   int nw = 16, lpr, r, occ = 1;
   if (K <= 16) { lpr = 64; r = 1; }
   else if (K <= 32) { lpr = 64; r = 2; }
@@ -430,7 +432,7 @@ inline bool pick_cfg(int64_t K, int V, int64_t ldx, PassCfg* cfg, bool panel = f
   }
   // lane offsets are 32-bit: (rows per wave - 1) * ldx + ldx must fit in bytes
   if ((uint64_t)(64 / lpr) * (uint64_t)ldx * 4u >= (1ull << 31)) return false;   // buffer offsets
-  *cfg = PassCfg{V, nw, lpr, r, occ};
+  *cfg = PassCfg{V, nw, lpr, r, occ, b16};
   return pass_cfg_supported(*cfg);
 }
 

@@ -1,6 +1,7 @@
 // gm_weiszfeld_f32 (include/gmagg.h): one Weiszfeld problem per call.  The entry point
 // validates and selects; the paths are run_gram, run_resident, run_resident_batched with
-// P = 1 (host_batched.hip) and run_stream.
+// P = 1 (host_batched.hip) and run_stream.  gm_weiszfeld_bf16 (client updates stored as
+// bf16) validates and runs run_stream on a bf16 tile.
 //
 // The host loop mirrors the reference's control flow (MNIST_Air_weight.py:145-160
 // for gm, 173-184 for gm2) but keeps every decision on the device: the
@@ -682,15 +683,16 @@ int select_rows(Call& q, PassCfg* cfg) {
   return kDeclined;
 }
 
-int validate_call(const gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
-                  const float* guess0, const float* out, const gm_opts* o) {
-  if (!c || !o || !out || !guess0) return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: NULL argument");
-  if (K < 1 || d < 1 || (ldx < d && o && o->layout == GM_LAYOUT_ROWS) || (!X)) return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: bad shape K=%lld d=%lld ldx=%lld", (long long)K, (long long)d, (long long)ldx);
-  if (o->maxiter < 0) return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: maxiter < 0");
+int validate_call(const gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t ldx,
+                  const float* guess0, const float* out, const gm_opts* o,
+                  const char* who = "gm_weiszfeld_f32") {
+  if (!c || !o || !out || !guess0) return fail(GM_ERR_INVALID, "%s: NULL argument", who);
+  if (K < 1 || d < 1 || (ldx < d && o && o->layout == GM_LAYOUT_ROWS) || (!X)) return fail(GM_ERR_INVALID, "%s: bad shape K=%lld d=%lld ldx=%lld", who, (long long)K, (long long)d, (long long)ldx);
+  if (o->maxiter < 0) return fail(GM_ERR_INVALID, "%s: maxiter < 0", who);
   if (o->mode != GM_MODE_IDEAL && o->mode != GM_MODE_AIRCOMP)
-    return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: unknown mode %d", o->mode);
+    return fail(GM_ERR_INVALID, "%s: unknown mode %d", who, o->mode);
   if (o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST && !o->noise_cb)
-    return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: GM_NOISE_HOST needs noise_cb");
+    return fail(GM_ERR_INVALID, "%s: GM_NOISE_HOST needs noise_cb", who);
   return GM_OK;
 }
 
@@ -738,4 +740,58 @@ extern "C" int gm_weiszfeld_f32(gm_ctx* c, const float* X, int64_t K, int64_t d,
   if (rc != kDeclined) return rc;
   return run_stream(c, X, K, d, ldx, guess0, out, o, res, cfg, s, tr, q.algo, panels,
                     q.guard_rejected, &q.oma);
+}
+
+// bf16 client updates: the streaming loop only, on the bf16 instantiation of the fused pass
+// (stream_pass_bf16.hip).  The element type travels in the tile (PassCfg.B16); the loop,
+// the K-space step, the draws and the timing are run_stream's.
+extern "C" int gm_weiszfeld_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                                 const float* guess0, float* out, const gm_opts* o,
+                                 gm_result* res, void* stream) {
+  static const char* const who = "gm_weiszfeld_bf16";
+  int rc = validate_call(c, X, K, d, ldx, guess0, out, o, who);
+  if (rc) return rc;
+  const bool panels = o->layout == GM_LAYOUT_PANELS;
+  if (o->layout != GM_LAYOUT_ROWS && !panels)
+    return fail(GM_ERR_INVALID, "%s: unknown layout %d", who, o->layout);
+  if (o->algo != GM_ALGO_AUTO && o->algo != GM_ALGO_STREAM)
+    return fail(GM_ERR_UNSUPPORTED, "%s: the streaming pass only (algo %d; the Gram, resident "
+                "and two-pass paths read fp32)", who, o->algo);
+  if (o->pre_oma)
+    return fail(GM_ERR_UNSUPPORTED, "%s: pre_oma is not supported (the noised values would be "
+                "rounded back to bf16)", who);
+  if (c->d_total > 0 || c->comm || c->ar_fn)
+    return fail(GM_ERR_UNSUPPORTED, "%s: sharded / collective contexts are not supported", who);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  if (o->maxiter == 0) {
+    HIPCHK(hipMemcpyAsync(out, guess0, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
+    gm_result r{};
+    r.last_movement = NAN;
+    if (res) *res = r;
+    return GM_OK;
+  }
+  PassCfg cfg{};
+  if (!pick_cfg(K, 8, ldx, &cfg, panels, true))
+    return fail(GM_ERR_UNSUPPORTED, "%s: no streaming tile for K=%lld (K <= 2048) at ldx=%lld",
+                who, (long long)K, (long long)ldx);
+  const int64_t W = (int64_t)cfg.LPR * cfg.V;
+  const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  if (panels) {
+    if (ldx < K * W || !aligned || ldx % 8 || K * W * 2 > 0x7fffffff)
+      return fail(GM_ERR_INVALID, "%s: panel layout needs panel stride >= K*W (%lld) and a "
+                  "multiple of 8, 16-byte aligned X, K*W*2 < 2^31 (ldx=%lld)", who,
+                  (long long)(K * W), (long long)ldx);
+  } else if (!aligned || ldx % 8 || d % 8) {
+    return fail(GM_ERR_UNSUPPORTED, "%s: row-major bf16 needs 16-byte aligned X with d and ldx "
+                "multiples of 8 (d=%lld ldx=%lld); pack panels (gm_rows_to_panels_bf16)", who,
+                (long long)d, (long long)ldx);
+  }
+  CallTraits tr{};
+  tr.d_total = d;
+  tr.host_noise = o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST;
+  PreOma none{};
+  return run_stream(c, reinterpret_cast<const float*>(X), K, d, ldx, guess0, out, o, res, cfg, s,
+                    tr, GM_ALGO_STREAM, panels, false, &none);
 }

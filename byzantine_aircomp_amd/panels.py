@@ -10,6 +10,11 @@ each chunk is ONE contiguous block of HBM.  It is the device-resident buffer a
 training loop writes client rows into (``store``), and ``gm2`` / ``gm`` accept it
 wherever they accept a ``[K, d]`` tensor; results are bit-identical to the
 row-major call (same chunks, same reduction order).
+
+``ClientPanels(..., dtype=torch.bfloat16)`` stores the values as bf16 in the layout of
+``gm_weiszfeld_bf16`` (W = ``gm_panel_width_bf16(K)``): half the bytes per streaming pass.
+``gm2`` / ``gm`` read them widened to fp32 (exact) and return fp32; the other aggregators
+take fp32 panels only.
 """
 from __future__ import annotations
 
@@ -19,25 +24,30 @@ from . import _lib
 
 __all__ = ["ClientPanels", "panel_width"]
 
+_DTYPES = (torch.float32, torch.bfloat16)
 
-def panel_width(K: int) -> int:
+
+def panel_width(K: int, dtype=torch.float32) -> int:
     """W of the panel layout for K clients (the streaming tile's chunk width)."""
-    w = int(_lib.load().gm_panel_width(int(K)))
+    lib = _lib.load()
+    w = int((lib.gm_panel_width_bf16 if dtype == torch.bfloat16 else lib.gm_panel_width)(int(K)))
     if w <= 0:
         raise ValueError(f"no panel layout for K={K}")
     return w
 
 
 class ClientPanels:
-    """K client vectors of length d, stored as ``data[ceil(d/W), K, W]`` fp32."""
+    """K client vectors of length d, stored as ``data[ceil(d/W), K, W]`` fp32 or bf16."""
 
-    def __init__(self, K: int, d: int, device=None, W: int | None = None):
+    def __init__(self, K: int, d: int, device=None, W: int | None = None, dtype=torch.float32):
+        if dtype not in _DTYPES:
+            raise TypeError(f"ClientPanels holds fp32 or bf16 (got {dtype})")
         self.K, self.d = int(K), int(d)
-        self.W = int(W) if W is not None else panel_width(K)
+        self.W = int(W) if W is not None else panel_width(K, dtype)
         self.npan = -(-self.d // self.W)
         dev = torch.device(device) if device is not None else torch.device("cuda")
         # zero-filled: the last panel's columns >= d stay 0
-        self.data = torch.zeros(self.npan, self.K, self.W, dtype=torch.float32, device=dev)
+        self.data = torch.zeros(self.npan, self.K, self.W, dtype=dtype, device=dev)
 
     # -- shape / metadata, so callers can treat it like the [K, d] matrix --------
     @property
@@ -78,19 +88,23 @@ class ClientPanels:
         if tuple(X.shape) != (self.K, self.d):
             raise ValueError(f"rows must be [{self.K}, {self.d}] (got {tuple(X.shape)})")
         X = X.to(self.device)
-        if X.device.type == "cuda" and X.dtype == torch.float32:
-            # one HIP kernel (pack.hip, gm_rows_to_panels_f32) instead of torch's
-            # transposed copy
+        # one HIP kernel (pack.hip) instead of torch's transposed copy; into bf16 panels
+        # the fp32 source is rounded to nearest even on the way (the bits of .to(bfloat16))
+        pack = {(torch.float32, torch.float32): "gm_rows_to_panels_f32",
+                (torch.float32, torch.bfloat16): "gm_rows_to_panels_bf16_from_f32",
+                (torch.bfloat16, torch.bfloat16): "gm_rows_to_panels_bf16"}.get(
+                    (X.dtype, self.dtype))
+        if X.device.type == "cuda" and pack:
             from . import _lib
             from .aggregators import context, _stream_ptr
             if X.stride(1) != 1 or X.stride(0) < self.d:
                 X = X.contiguous()
             ctx = context(X.device)
             with torch.cuda.device(X.device):
-                _lib.check(ctx.lib.gm_rows_to_panels_f32(
+                _lib.check(getattr(ctx.lib, pack)(
                     ctx.handle, X.data_ptr(), self.K, self.d, max(X.stride(0), self.d),
                     self.data.data_ptr(), self.W, self.panel_stride, _stream_ptr(X.device)),
-                    "gm_rows_to_panels_f32")
+                    pack)
             return self
         nf = self._full()
         with torch.no_grad():
@@ -102,10 +116,14 @@ class ClientPanels:
         return self
 
     @classmethod
-    def from_rows(cls, X: torch.Tensor, device=None) -> "ClientPanels":
+    def from_rows(cls, X: torch.Tensor, device=None, dtype=None) -> "ClientPanels":
+        """Panels of a row-major [K, d] matrix.  dtype: X's own if that is bf16, else fp32;
+        ``dtype=torch.bfloat16`` on an fp32 matrix rounds to nearest even while packing."""
         K, d = X.shape
+        if dtype is None:
+            dtype = torch.bfloat16 if X.dtype == torch.bfloat16 else torch.float32
         p = cls(K, d, device=device if device is not None else
-                (X.device if X.device.type == "cuda" else None))
+                (X.device if X.device.type == "cuda" else None), dtype=dtype)
         return p.copy_rows_(X)
 
     def row(self, k: int) -> torch.Tensor:
@@ -116,7 +134,7 @@ class ClientPanels:
         return self.data.transpose(0, 1).reshape(self.K, self.npan * self.W)[:, : self.d].contiguous()
 
     def mean(self, dim: int = 0) -> torch.Tensor:
-        """Column mean (gm2's default guess, M:167)."""
+        """Column mean (gm2's default guess, M:167); fp32, of the widened values for bf16."""
         if dim != 0:
             raise ValueError("ClientPanels.mean supports dim=0 only")
-        return self.data.mean(dim=1).reshape(-1)[: self.d]
+        return self.data.mean(dim=1, dtype=torch.float32).reshape(-1)[: self.d]

@@ -29,6 +29,13 @@
  * W = gm_panel_width(K) and ldx = elements between panels (>= K*W); element
  * (k, j) at X[(j/W)*ldx + k*W + j%W].  Each streaming-pass chunk is then one
  * contiguous block of HBM.
+ *
+ * bf16 client updates: gm_weiszfeld_bf16 reads X stored as bfloat16 (uint16_t bit
+ * patterns), half the bytes per pass.  Only X is 16-bit: a bf16 value widens to fp32
+ * exactly (bits << 16), and the guess, the iterates, the output and every sum are what
+ * gm_weiszfeld_f32 has, so the result is gm_weiszfeld_f32's on the widened matrix up to
+ * the order of the column sums.  Its panel layout is [ceil(d/W)][K][W] bf16 with
+ * W = gm_panel_width_bf16(K) (twice gm_panel_width(K): the same bytes per row segment).
  */
 #ifndef GMAGG_H
 #define GMAGG_H
@@ -39,7 +46,7 @@
 extern "C" {
 #endif
 
-#define GMAGG_ABI_VERSION 4
+#define GMAGG_ABI_VERSION 5
 
 enum gm_status {
     GM_OK = 0,
@@ -187,6 +194,24 @@ int gm_weiszfeld_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t 
  * tile's chunk width: 32 columns at 512 < K <= 1024); 0 if K is unsupported. */
 int64_t gm_panel_width(int64_t K);
 
+/* gm2 / gm on client updates stored as bf16: X holds bfloat16 bit patterns, row-major
+ * [K][ldx] (opts->layout = GM_LAYOUT_ROWS) or panels [ceil(d/W)][K][W] with
+ * W = gm_panel_width_bf16(K) and ldx = elements between panels (>= K*W, a multiple of 8).
+ * guess0 and out are fp32; opts, the modes (gm2 and AirComp gm, Philox or host draws),
+ * maxiter == 0 and gm_ctx_pass_timing are as for gm_weiszfeld_f32.  It runs the fused
+ * streaming pass only: result->algo_used is GM_ALGO_STREAM.
+ * GM_ERR_UNSUPPORTED (with a message) for: an algo other than GM_ALGO_AUTO / GM_ALGO_STREAM;
+ * pre_oma; a sharded or collective context (gm_ctx_set_shard, gm_ctx_set_allreduce,
+ * gm_ctx_init_rccl); K > 2048; a row-major X that is not 16-byte aligned with d and ldx
+ * multiples of 8 (pack it: gm_rows_to_panels_bf16).  X is never written. */
+int gm_weiszfeld_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                      const float* guess0, float* out, const gm_opts* opts,
+                      gm_result* result, void* stream);
+
+/* Panel width W of gm_weiszfeld_bf16's panel layout for K clients (the bf16 streaming
+ * tile's chunk width: 64 columns at 512 < K <= 1024); 0 if K is unsupported. */
+int64_t gm_panel_width_bf16(int64_t K);
+
 /* Batched independent problems (BASELINE config C5, the draw.ipynb-style sweep
  * over many small aggregations): problem p aggregates the K rows at X + p*ldp
  * (row stride ldx) from guess0 + p*ldg into out + p*ldo.  One launch per pass
@@ -281,6 +306,16 @@ int gm_oma_philox_panels_f32(gm_ctx* ctx, float* X, int64_t K, int64_t d, int64_
  * (GM_LAYOUT_PANELS).  Padding columns >= d are not written. */
 int gm_rows_to_panels_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx,
                           float* P, int64_t W, int64_t panel_stride, void* stream);
+
+/* The same packing into bf16 panels (gm_weiszfeld_bf16's layout, W = gm_panel_width_bf16(K)),
+ * from row-major fp32 — rounded to nearest even, the bits of torch's .to(torch.bfloat16)
+ * for finite values and infinities (NaN becomes 0x7FC0) — or from row-major bf16.
+ * Padding columns >= d are not written. */
+int gm_rows_to_panels_bf16_from_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d,
+                                    int64_t ldx, uint16_t* P, int64_t W, int64_t panel_stride,
+                                    void* stream);
+int gm_rows_to_panels_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                           uint16_t* P, int64_t W, int64_t panel_stride, void* stream);
 
 /* The K clients' local SGD steps of one federated step (the loop body M:291-343:
  * forward, CrossEntropyLoss (mean), backward, p -= gamma * (grad + weight_decay * p),
