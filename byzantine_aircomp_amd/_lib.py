@@ -62,6 +62,25 @@ class GmResult(C.Structure):
     ]
 
 
+class GmCclipOpts(C.Structure):
+    _fields_ = [
+        ("tau", C.c_double),
+        ("maxiter", C.c_int64),
+        ("tol", C.c_double),
+        ("layout", C.c_int32),
+        ("check_every", C.c_int32),
+    ]
+
+
+class GmCclipResult(C.Structure):
+    _fields_ = [
+        ("iters", C.c_int64),
+        ("last_movement", C.c_double),
+        ("converged", C.c_int32),
+        ("clipped", C.c_int32),
+    ]
+
+
 # (name, restype, argtypes) for every symbol the header declares.
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -78,6 +97,10 @@ SIGNATURES = [
     ("gm_weiszfeld_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, C.POINTER(GmOpts),
                                     C.POINTER(GmResult), _P]),
     ("gm_panel_width_bf16", _I64, [_I64]),
+    ("gm_cclip_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, C.POINTER(GmCclipOpts),
+                               C.POINTER(GmCclipResult), _P]),
+    ("gm_cclip_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, C.POINTER(GmCclipOpts),
+                                C.POINTER(GmCclipResult), _P]),
     ("gm_weiszfeld_batched_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
                                            _I64, C.POINTER(GmOpts), C.POINTER(GmResult), _P]),
     ("gm_mean_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),

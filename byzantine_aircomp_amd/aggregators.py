@@ -34,6 +34,11 @@ the fused streaming pass reads them widened to fp32, which is exact, at half the
 pass; guess, iterates and result are fp32.  The other aggregators are fp32 only.  The trace
 of the last call (iterations, last movement) is in ``last_result``.
 
+Beyond the reference: ``cclip(wList, options)``, centered clipping (Karimireddy, He & Jaggi,
+ICML 2021) with the same contract and inputs as ``gm2`` on the same streaming pass; options
+``tau`` (required), ``clip_iters`` (1), ``clip_tol`` (None), ``guess`` (zeros);
+``cclip.with_options(tau=...)`` makes an ``aggregate`` for loops that build the dict.
+
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
 from __future__ import annotations
@@ -49,7 +54,7 @@ import torch
 from . import _lib
 from .panels import ClientPanels
 
-__all__ = ["gm2", "gm", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
+__all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance"]
 
 
@@ -214,6 +219,22 @@ def _bf16_operand(X: torch.Tensor):
     return P.data, P.panel_stride, _lib.GM_LAYOUT_PANELS
 
 
+def _client_operand(wList):
+    """(tensor, ldx, layout, K, d) of the client matrix the streaming pass reads (gm2, gm,
+    cclip): ClientPanels as they are, a bf16 [K, d] tensor through _bf16_operand, an fp32 one
+    through _rows; CPU tensors staged to the GPU.  wList is never written."""
+    if isinstance(wList, ClientPanels):
+        K, d = wList.shape
+        return wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS, K, d
+    if wList.dtype == torch.bfloat16:
+        K, d = wList.shape
+        X, ldx, layout = _bf16_operand(_stage(wList, bf16_ok=True))
+        return X, ldx, layout, K, d
+    X, ldx = _rows(_stage(wList))
+    K, d = X.shape
+    return X, ldx, _lib.GM_LAYOUT_ROWS, K, d
+
+
 def _noise_source(options) -> int:
     src = options.get("noise_source", os.environ.get("BYZ_AIRCOMP_NOISE", "device"))
     if src == "device":
@@ -277,17 +298,7 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
             OMA(wList, float(pre_var), seed=pre_seed)
         last_result = GMResult(0, float("nan"), False, "none")
         return guess
-    layout = _lib.GM_LAYOUT_ROWS
-    if isinstance(wList, ClientPanels):
-        X, ldx, layout = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
-        K, d = wList.shape
-    elif bf16:
-        K, d = wList.shape
-        X, ldx, layout = _bf16_operand(_stage(wList, bf16_ok=True))
-    else:
-        X = _stage(wList)
-        X, ldx = _rows(X)
-        K, d = X.shape
+    X, ldx, layout, K, d = _client_operand(wList)
     g0 = guess.detach().to(device=X.device, dtype=torch.float32).contiguous()
     if g0.numel() != d:
         raise ValueError(f"guess has {g0.numel()} elements, wList rows have {d}")
@@ -345,6 +356,100 @@ def gm(wList, options={}):  # noqa: B006 - the reference's signature (M:131)
     """AirComp Weiszfeld geometric median (MNIST_Air_weight.py:131-160).  fp32 or bf16 client
     updates; the result is fp32 either way."""
     return _weiszfeld(wList, options, aircomp=True)
+
+
+_CCLIP_KEYS = ("tau", "clip_iters", "clip_tol")
+
+
+def _cclip_params(options):
+    """(tau, clip_iters, tol for the library) from the options; ValueError on a missing or
+    invalid value, before anything touches a GPU."""
+    if options.get("tau") is None:
+        raise ValueError("cclip needs options['tau'] (the clipping radius; there is no default)")
+    tau = float(options["tau"])
+    if not tau > 0:                                   # NaN fails too; +inf is the mean step
+        raise ValueError(f"cclip: tau must be > 0 (got {options['tau']!r})")
+    iters = int(options.get("clip_iters", 1))
+    if iters < 0:
+        raise ValueError(f"cclip: clip_iters must be >= 0 (got {iters})")
+    ctol = options.get("clip_tol")
+    if ctol is not None and not float(ctol) >= 0:
+        raise ValueError(f"cclip: clip_tol must be None or >= 0 (got {ctol!r})")
+    # None: exactly clip_iters iterations (a negative tol never passes the movement test)
+    return tau, iters, -1.0 if ctol is None else float(ctol)
+
+
+def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+    """Centered clipping (Karimireddy, He & Jaggi, ICML 2021, Algorithm 2), not one of the
+    reference's aggregators: from v = options['guess'] (default the zero vector, as in the
+    authors' code; pass the previous aggregate or the current model for the paper's use),
+    ``clip_iters`` (default 1) times
+
+        v <- v + mean_k (x_k - v) * min(1, tau / ||x_k - v||)
+
+    on the fused streaming pass: one read of wList per iteration plus one for the first
+    distances.  ``options['tau']`` is required.  ``clip_tol`` (default None: run exactly
+    clip_iters iterations) stops early once the fp32 movement ||v - v'|| <= clip_tol,
+    returning v'.  Every other key (maxiter, tol, eta, honestSize, noise_var, ...) is ignored.
+    wList: an fp32 or bf16 [K, d] tensor or ClientPanels, staged as for gm2 and never written;
+    the result is fp32 on wList.device.  ``clip_iters == 0`` returns the guess object.
+    ``last_result`` holds the trace, ``cclip.last_info['clipped']`` the number of clients
+    outside the radius at the last iteration run."""
+    global last_result
+    options = options or {}
+    tau, iters, tol = _cclip_params(options)
+    if not isinstance(wList, ClientPanels) and wList.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"cclip reads fp32 or bf16 client updates (got {wList.dtype})")
+    guess = options.get("guess")
+    if guess is None:
+        guess = torch.zeros(wList.shape[1], dtype=torch.float32, device=wList.device)
+    if iters == 0:
+        last_result = GMResult(0, float("nan"), False, "none")
+        cclip.last_info = {"clipped": 0}
+        return guess
+    X, ldx, layout, K, d = _client_operand(wList)
+    g0 = guess.detach().to(device=X.device, dtype=torch.float32).contiguous()
+    if g0.numel() != d:
+        raise ValueError(f"guess has {g0.numel()} elements, wList rows have {d}")
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    if d == 0:
+        last_result = GMResult(1, 0.0, True, "none")
+        cclip.last_info = {"clipped": 0}
+        return out.to(wList.device)
+    o = _lib.GmCclipOpts()
+    o.tau, o.maxiter, o.tol, o.layout = tau, iters, tol, layout
+    o.check_every = int(options.get("check_every", 0))
+    res = _lib.GmCclipResult()
+    ctx = context(X.device)
+    fn = "gm_cclip_bf16" if X.dtype == torch.bfloat16 else "gm_cclip_f32"
+    with torch.cuda.device(X.device):
+        _lib.check(getattr(ctx.lib, fn)(ctx.handle, X.data_ptr(), K, d, ldx, g0.data_ptr(),
+                                        out.data_ptr(), C.byref(o), C.byref(res),
+                                        _stream_ptr(X.device)), fn)
+    last_result = GMResult(res.iters, res.last_movement, bool(res.converged), "stream")
+    cclip.last_info = {"clipped": int(res.clipped)}
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+def _cclip_with_options(**fixed):
+    """An ``aggregate(wList, options)`` callable named "cclip" that applies tau / clip_iters /
+    clip_tol over the caller's options, for loops that build the dict themselves
+    (training.run(..., aggregate=cclip.with_options(tau=10.0)), the reference's
+    eval(args.agg))."""
+    unknown = sorted(set(fixed) - set(_CCLIP_KEYS))
+    if unknown:
+        raise TypeError(f"cclip.with_options takes {', '.join(_CCLIP_KEYS)} (got {unknown})")
+    _cclip_params(fixed if "tau" in fixed else dict(fixed, tau=1.0))   # bad values fail here
+
+    def aggregate(wList, options={}):  # noqa: B006
+        return cclip(wList, {**(options or {}), **fixed})
+    aggregate.__name__ = aggregate.__qualname__ = "cclip"
+    aggregate.__doc__ = f"cclip with {fixed}"
+    return aggregate
+
+
+cclip.with_options = _cclip_with_options
+cclip.last_info = {"clipped": 0}
 
 
 def _coordinate(wList, fn_name, *extra):

@@ -15,13 +15,14 @@ struct alignas(64) KState {
   int32_t converged;
   int64_t iters;         // loop bodies executed
   double last_movement;  // fp32 movement of the last body, widened
-  float a_noise;         // scale of the per-column noise in the next pass (AIRCOMP)
+  float a_noise;         // scale of the next pass's column term: the per-column noise
+                         // (AIRCOMP), or the old iterate's 1 - sum_k c_k (centered clipping)
   float s;               // scaler sqrt(mean(g^2)) of the current iterate (AIRCOMP)
   // Gram variant, written by gram_solve for the AUTO accuracy guard (host_weiszfeld.hip):
   double guard_q;        // ||X'^T b||: one-step error of the K-space map (gram_verify)
   double guard_r;        // last / previous K-space movement (contraction estimate)
   int32_t gram_bad;      // the reduced Gram has a non-finite entry (f16 overflow or input)
-  int32_t pad0;
+  int32_t clipped;       // centered clipping: clients with dist_k > tau at the last coefficients
   double pad1;
 };
 
@@ -46,8 +47,9 @@ struct PassArgs {
   const KState* st;
   double* slab;           // [gridDim.x][slab_stride] per-block partial sums
   int64_t slab_stride;
-  // additive column noise of the AirComp variant (STEP)
-  int noise;              // 0 none, 1 Philox, 2 host-supplied column draws
+  // column term of the STEP pass: g' = sum_k c_k x_k + a_noise * term (the AirComp variant's
+  // additive noise, or centered clipping's old iterate)
+  int noise;              // 0 none, 1 Philox, 2 host-supplied column draws, 3 g_old (cclip)
   const float* hnoise;    // noise == 2: local column draws (d floats)
   uint64_t seed;
   int64_t iter;           // Weiszfeld iteration index the pass computes
@@ -89,9 +91,14 @@ constexpr uint64_t kSeedStride = 0x9E3779B97F4A7C15ull;
 // (the count window the tests check counts against; measured: profiles/r5s1_movement_floor.txt)
 constexpr double kFloorUlps = 2.0;
 
+// KspaceArgs.mode beyond the public gm_mode values: centered clipping (gm_cclip_f32 / _bf16;
+// Karimireddy, He & Jaggi 2021, Algorithm 2), c_k = min(1, tau / dist_k) / K and the old
+// iterate weighted a = 1 - sum_k c_k.  The streaming loop only.
+constexpr int kModeCclip = 2;
+
 struct KspaceArgs {
   int64_t K, d_total, t;  // t = pass just completed, -1 after the initial pass
-  int mode;               // gm_mode
+  int mode;               // gm_mode, or kModeCclip
   int has_noise, noise_src;
   float tol, eps;
   double P_max, noise_sd; // noise_sd = sqrt(noise_var / 2) (OMA2, M:410)
@@ -108,10 +115,13 @@ struct KspaceArgs {
   int64_t sums_ps;
   int* n_done;            // problems whose tol test has fired (nullable)
   KState* mirror;         // host-mapped copy of *st written at the end (nullable, one problem)
+  double tau;             // kModeCclip: the clipping radius (> 0, +inf allowed)
 };
 
 // Streaming pass (stream_pass.hip).  mode: 0 step, 1 init, 2 init + ||x_k||^2, 3 Gram
-// closing sum, 4 init after OMA pre-noise written back to X (V = 4 tiles).
+// closing sum, 4 init after OMA pre-noise written back to X (V = 4 tiles), kPassStepSelf a
+// STEP pass whose column term is the old iterate (centered clipping; PassArgs.noise = 3).
+constexpr int kPassStepSelf = 5;
 hipError_t launch_pass(const PassCfg& cfg, int mode, int grid, const PassArgs& a, hipStream_t s,
                        int problems = 1);
 int pass_blocks_per_cu(const PassCfg& cfg, int mode);
@@ -123,6 +133,9 @@ int pass_variant();   // GMAGG_PASS_VARIANT (stream_pass.hip), -1 unset
 // The bf16-input instantiations (stream_pass_bf16.hip): the tiles pick_cfg returns, modes
 // 0-2, both layouts, the plain and the rolling schedule; nullptr for anything else.
 const void* pass_kernel_bf16(const PassCfg& cfg, int mode, bool panel);
+// The fp32 STEP instantiations with the old iterate as column term (stream_pass_cclip.hip):
+// every tile and schedule launch_pass would pick for mode 0; nullptr for anything else.
+const void* pass_kernel_self(const PassCfg& cfg, bool panel);
 
 // Reduction, K-space step and the two-pass path (weiszfeld.hip).
 hipError_t launch_slab_reduce(const double* slab, int nb, int64_t S, double* sums,

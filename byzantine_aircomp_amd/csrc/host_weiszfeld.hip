@@ -1,7 +1,8 @@
 // gm_weiszfeld_f32 (include/gmagg.h): one Weiszfeld problem per call.  The entry point
 // validates and selects; the paths are run_gram, run_resident, run_resident_batched with
 // P = 1 (host_batched.hip) and run_stream.  gm_weiszfeld_bf16 (client updates stored as
-// bf16) validates and runs run_stream on a bf16 tile.
+// bf16) validates and runs run_stream on a bf16 tile.  gm_cclip_f32 / gm_cclip_bf16 (centered
+// clipping) run the same loop with the clipping rule in the K-space step.
 //
 // The host loop mirrors the reference's control flow (MNIST_Air_weight.py:145-160
 // for gm, 173-184 for gm2) but keeps every decision on the device: the
@@ -26,6 +27,7 @@ struct CallTraits {
   int64_t d_total, col_off;
   bool host_noise;   // AirComp with the caller's draws (GM_NOISE_HOST)
   bool collective;   // sharded, or an all-reduce (RCCL, callback) is set: no resident path
+  double cclip_tau;  // > 0: centered clipping (gm_cclip_*; the options' mode is kModeCclip)
 };
 
 // pre_oma: the reference's OMA(weight_f, var) before a non-gm aggregator (M:351-352),
@@ -287,14 +289,14 @@ again:
 
 // Grids of the streaming loop's STEP and INIT passes (algo: GM_ALGO_STREAM or _TWOPASS).
 void stream_grids(const gm_ctx* c, int64_t K, int64_t d, int algo, const PassCfg& cfg,
-                  const PassCfg& cfg_i, int init_mode, int* nb_step, int* nb_init) {
+                  const PassCfg& cfg_i, int init_mode, int step_mode, int* nb_step, int* nb_init) {
   if (algo != GM_ALGO_STREAM) {
     *nb_step = *nb_init = twopass_blocks(K, d, c->num_cu);
     return;
   }
   const int J = cfg.LPR * cfg.V, Ji = cfg_i.LPR * cfg_i.V;
   const int64_t nch = (d + J - 1) / J, nchi = (d + Ji - 1) / Ji;
-  const int64_t cap_s = (int64_t)c->num_cu * pass_blocks_per_cu(cfg, 0);
+  const int64_t cap_s = (int64_t)c->num_cu * pass_blocks_per_cu(cfg, step_mode);
   const int64_t cap_i = (int64_t)c->num_cu * pass_blocks_per_cu(cfg_i, init_mode);
   *nb_step = (int)std::max<int64_t>(1, std::min(nch, cap_s));
   *nb_init = (int)std::max<int64_t>(1, std::min(nchi, cap_i));
@@ -305,15 +307,21 @@ void stream_grids(const gm_ctx* c, int64_t K, int64_t d, int algo, const PassCfg
 // of its partials and the K-space step.  panels: X in the panel layout, ldx its panel
 // stride, cfg the panel tile (used for INIT too).  oma: the pre-noise still to apply, if
 // any, fused into INIT where the tile allows.
+// Centered clipping (tr.cclip_tau > 0, o->mode = kModeCclip) is the same loop: the K-space
+// step's third rule, and the STEP pass's column term is the old iterate (noise kind 3).
+// final_state: the KState the result was taken from (nullable).
 int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, const float* guess0,
                float* out, const gm_opts* o, gm_result* res, const PassCfg& cfg, hipStream_t s,
-               const CallTraits& tr, int algo, bool panels, bool guard_rejected, PreOma* oma) {
+               const CallTraits& tr, int algo, bool panels, bool guard_rejected, PreOma* oma,
+               KState* final_state = nullptr) {
   const bool host_noise = tr.host_noise;
   const int64_t d_total = tr.d_total, col_off = tr.col_off;
   const int init_mode = o->mode == GM_MODE_AIRCOMP ? 2 : 1;   // ||x_k||^2 only for AirComp
   const PassCfg cfg_i = panels ? cfg : light_cfg(K, cfg);
   int nb_step, nb_init;
-  stream_grids(c, K, d, algo, cfg, cfg_i, init_mode, &nb_step, &nb_init);
+  // centered clipping: the STEP instantiation whose column term is the old iterate
+  const int step_mode = tr.cclip_tau > 0 ? kPassStepSelf : 0;
+  stream_grids(c, K, d, algo, cfg, cfg_i, init_mode, step_mode, &nb_step, &nb_init);
   const int nb = std::max(nb_step, nb_init);
   Workspace w;
   int rc = ensure_ws(c, K, d, nb, &w);
@@ -324,8 +332,9 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
   KState* hslot = host_lagged(c);
   HIPCHK(hipMemsetAsync(w.st, 0, sizeof(KState), s));
 
-  const int noise_kind = !aircomp_noise(o) ? 0 : (host_noise ? 2 : 1);
+  const int noise_kind = tr.cclip_tau > 0 ? 3 : !aircomp_noise(o) ? 0 : (host_noise ? 2 : 1);
   KspaceArgs ka = kspace_args(K, d_total, o);
+  ka.tau = tr.cclip_tau;
   ka.noise_src = host_noise ? 1 : 0;
   ka.sums = w.sums;
   ka.r = w.r;
@@ -358,7 +367,7 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
       a.noise = noise_kind; a.hnoise = w.hnoise; a.seed = o->seed; a.iter = t; a.col_off = col_off;
       a.panel_stride = panels ? ldx : 0;
       a.chunk_pair = panels ? 0 : chunk_pair(c, init ? cfg_i : cfg, init ? nb_init : nb_step);
-      int mode = init ? init_mode : 0;
+      int mode = init ? init_mode : step_mode;
       if (init) {
         // the fused OMA needs float4 groups = Philox blocks: V = 4, 4-aligned shards
         int rco = oma->fuse_or_apply(cfg_i.V == 4 && col_off % 4 == 0 && init_mode == 1, &a, &mode);
@@ -460,6 +469,7 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
   for (int64_t k = r.iters; k < enqueued; ++k) drop_last_timing(c);
   HIPCHK(hipMemcpyAsync(out, w.g[(r.iters - 1) & 1], sizeof(float) * d, hipMemcpyDeviceToDevice, s));
   if (res) *res = r;
+  if (final_state) *final_state = *final_st;
   return GM_OK;
 }
 
@@ -696,7 +706,166 @@ int validate_call(const gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t 
   return GM_OK;
 }
 
+// bf16 client updates run on one device's streaming pass only.
+int bf16_refuse_collective(const gm_ctx* c, const char* who) {
+  if (c->d_total > 0 || c->comm || c->ar_fn)
+    return fail(GM_ERR_UNSUPPORTED, "%s: sharded / collective contexts are not supported", who);
+  return GM_OK;
+}
+
+// The bf16 streaming tile of a call, and whether the kernel can read this X in place.
+int bf16_tile(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, bool panels, PassCfg* cfg,
+              const char* who) {
+  if (!pick_cfg(K, 8, ldx, cfg, panels, true))
+    return fail(GM_ERR_UNSUPPORTED, "%s: no streaming tile for K=%lld (K <= 2048) at ldx=%lld",
+                who, (long long)K, (long long)ldx);
+  const int64_t W = (int64_t)cfg->LPR * cfg->V;
+  const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  if (panels) {
+    if (ldx < K * W || !aligned || ldx % 8 || K * W * 2 > 0x7fffffff)
+      return fail(GM_ERR_INVALID, "%s: panel layout needs panel stride >= K*W (%lld) and a "
+                  "multiple of 8, 16-byte aligned X, K*W*2 < 2^31 (ldx=%lld)", who,
+                  (long long)(K * W), (long long)ldx);
+  } else if (!aligned || ldx % 8 || d % 8) {
+    return fail(GM_ERR_UNSUPPORTED, "%s: row-major bf16 needs 16-byte aligned X with d and ldx "
+                "multiples of 8 (d=%lld ldx=%lld); pack panels (gm_rows_to_panels_bf16)", who,
+                (long long)d, (long long)ldx);
+  }
+  return GM_OK;
+}
+
+// maxiter == 0: the loop body never runs and the guess is the result.
+int copy_guess(const float* guess0, float* out, int64_t d, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(out, guess0, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
+  return GM_OK;
+}
+
+// ---- centered clipping -------------------------------------------------------------------
+
+int validate_cclip(const gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t ldx,
+                   const float* guess0, const float* out, const gm_cclip_opts* o, const char* who) {
+  if (!c || !o || !out || !guess0 || !X) return fail(GM_ERR_INVALID, "%s: NULL argument", who);
+  if (o->layout != GM_LAYOUT_ROWS && o->layout != GM_LAYOUT_PANELS)
+    return fail(GM_ERR_INVALID, "%s: unknown layout %d", who, o->layout);
+  if (K < 1 || d < 1 || (ldx < d && o->layout == GM_LAYOUT_ROWS))
+    return fail(GM_ERR_INVALID, "%s: bad shape K=%lld d=%lld ldx=%lld", who, (long long)K,
+                (long long)d, (long long)ldx);
+  if (o->maxiter < 0) return fail(GM_ERR_INVALID, "%s: maxiter < 0", who);
+  if (!(o->tau > 0.0))   // NaN fails too
+    return fail(GM_ERR_INVALID, "%s: tau must be > 0 (+inf allowed; got %g)", who, o->tau);
+  return GM_OK;
+}
+
+// The loop's options for a clipping call: run_stream reads maxiter, tol, check_every and the
+// mode (kModeCclip: no AirComp draws, INIT without the row norms).
+gm_opts cclip_loop_opts(const gm_cclip_opts* o) {
+  gm_opts g{};
+  g.maxiter = o->maxiter;
+  g.tol = o->tol;
+  g.mode = kModeCclip;
+  g.algo = GM_ALGO_STREAM;
+  g.check_every = o->check_every;
+  g.layout = o->layout;
+  return g;
+}
+
+void cclip_result(const gm_result& r, const KState& st, gm_cclip_result* res) {
+  if (!res) return;
+  res->iters = r.iters;
+  res->last_movement = r.last_movement;
+  res->converged = r.converged;
+  res->clipped = st.clipped;
+}
+
+int cclip_no_iteration(const float* guess0, float* out, int64_t d, gm_cclip_result* res,
+                       hipStream_t s) {
+  int rc = copy_guess(guess0, out, d, s);
+  if (rc) return rc;
+  if (res) {
+    *res = gm_cclip_result{};
+    res->last_movement = NAN;
+  }
+  return GM_OK;
+}
+
 }  // namespace
+
+// Centered clipping on fp32 client updates: run_stream's loop with the clipping rule in the
+// K-space step, on the fused pass (K <= 2048; rows or panels) or the two-pass kernels
+// (row-major, any K).  d-sharded contexts as gm2: the coefficients, a and the stop decision
+// come from the all-reduced sums, the same on every rank.
+extern "C" int gm_cclip_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
+                            const float* guess0, float* out, const gm_cclip_opts* o,
+                            gm_cclip_result* res, void* stream) {
+  static const char* const who = "gm_cclip_f32";
+  int rc = validate_cclip(c, X, K, d, ldx, guess0, out, o, who);
+  if (rc) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  if (o->maxiter == 0) return cclip_no_iteration(guess0, out, d, res, s);
+  CallTraits tr{};
+  tr.sharded = c->d_total > 0;
+  tr.d_total = tr.sharded ? c->d_total : d;
+  tr.col_off = tr.sharded ? c->d_offset : 0;
+  tr.collective = tr.sharded || c->comm || c->ar_fn;
+  tr.cclip_tau = o->tau;
+  const bool panels = o->layout == GM_LAYOUT_PANELS;
+  PassCfg cfg{};
+  int algo = GM_ALGO_STREAM;
+  if (panels) {
+    const int64_t W = gm_panel_width(K);
+    if (!panel_cfg(K, W, &cfg))
+      return fail(GM_ERR_UNSUPPORTED, "%s: panel layout: no streaming tile of width %lld for "
+                  "K=%lld", who, (long long)W, (long long)K);
+    if (ldx < K * W || (reinterpret_cast<uintptr_t>(X) & 15) || K * W * 4 > 0x7fffffff)
+      return fail(GM_ERR_INVALID, "%s: panel layout: need panel stride >= K*W (%lld), 16-byte "
+                  "aligned X, K*W*4 < 2^31 (ldx=%lld)", who, (long long)(K * W), (long long)ldx);
+  } else if (!pick_cfg(K, pick_vec(X, d, ldx), ldx, &cfg)) {
+    algo = GM_ALGO_TWOPASS;   // K > 2048 (or rows too far apart for the tile's lane offsets)
+  }
+  const gm_opts lo = cclip_loop_opts(o);
+  PreOma none{};
+  gm_result r{};
+  KState fin{};
+  rc = run_stream(c, X, K, d, ldx, guess0, out, &lo, &r, cfg, s, tr, algo, panels, false, &none,
+                  &fin);
+  if (rc) return rc;
+  cclip_result(r, fin, res);
+  return GM_OK;
+}
+
+// Centered clipping on bf16 client updates: the bf16 instantiation of the fused pass, under
+// gm_weiszfeld_bf16's rules (one device, K <= 2048, rows readable in place or panels).
+extern "C" int gm_cclip_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                             const float* guess0, float* out, const gm_cclip_opts* o,
+                             gm_cclip_result* res, void* stream) {
+  static const char* const who = "gm_cclip_bf16";
+  int rc = validate_cclip(c, X, K, d, ldx, guess0, out, o, who);
+  if (rc) return rc;
+  rc = bf16_refuse_collective(c, who);
+  if (rc) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  if (o->maxiter == 0) return cclip_no_iteration(guess0, out, d, res, s);
+  const bool panels = o->layout == GM_LAYOUT_PANELS;
+  PassCfg cfg{};
+  rc = bf16_tile(X, K, d, ldx, panels, &cfg, who);
+  if (rc) return rc;
+  CallTraits tr{};
+  tr.d_total = d;
+  tr.cclip_tau = o->tau;
+  const gm_opts lo = cclip_loop_opts(o);
+  PreOma none{};
+  gm_result r{};
+  KState fin{};
+  rc = run_stream(c, reinterpret_cast<const float*>(X), K, d, ldx, guess0, out, &lo, &r, cfg, s,
+                  tr, GM_ALGO_STREAM, panels, false, &none, &fin);
+  if (rc) return rc;
+  cclip_result(r, fin, res);
+  return GM_OK;
+}
 
 extern "C" int gm_weiszfeld_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
                                 const float* guess0, float* out, const gm_opts* o,
@@ -760,34 +929,22 @@ extern "C" int gm_weiszfeld_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_
   if (o->pre_oma)
     return fail(GM_ERR_UNSUPPORTED, "%s: pre_oma is not supported (the noised values would be "
                 "rounded back to bf16)", who);
-  if (c->d_total > 0 || c->comm || c->ar_fn)
-    return fail(GM_ERR_UNSUPPORTED, "%s: sharded / collective contexts are not supported", who);
+  rc = bf16_refuse_collective(c, who);
+  if (rc) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   WsOrder order(c, s);
   HIPCHK(order.err);
   if (o->maxiter == 0) {
-    HIPCHK(hipMemcpyAsync(out, guess0, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
+    rc = copy_guess(guess0, out, d, s);
+    if (rc) return rc;
     gm_result r{};
     r.last_movement = NAN;
     if (res) *res = r;
     return GM_OK;
   }
   PassCfg cfg{};
-  if (!pick_cfg(K, 8, ldx, &cfg, panels, true))
-    return fail(GM_ERR_UNSUPPORTED, "%s: no streaming tile for K=%lld (K <= 2048) at ldx=%lld",
-                who, (long long)K, (long long)ldx);
-  const int64_t W = (int64_t)cfg.LPR * cfg.V;
-  const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  if (panels) {
-    if (ldx < K * W || !aligned || ldx % 8 || K * W * 2 > 0x7fffffff)
-      return fail(GM_ERR_INVALID, "%s: panel layout needs panel stride >= K*W (%lld) and a "
-                  "multiple of 8, 16-byte aligned X, K*W*2 < 2^31 (ldx=%lld)", who,
-                  (long long)(K * W), (long long)ldx);
-  } else if (!aligned || ldx % 8 || d % 8) {
-    return fail(GM_ERR_UNSUPPORTED, "%s: row-major bf16 needs 16-byte aligned X with d and ldx "
-                "multiples of 8 (d=%lld ldx=%lld); pack panels (gm_rows_to_panels_bf16)", who,
-                (long long)d, (long long)ldx);
-  }
+  rc = bf16_tile(X, K, d, ldx, panels, &cfg, who);
+  if (rc) return rc;
   CallTraits tr{};
   tr.d_total = d;
   tr.host_noise = o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST;

@@ -22,7 +22,8 @@
 // slab_reduce in a fixed order: deterministic, no atomics.
 //
 // The kernel template is in stream_pass_kernel.h; this file instantiates it for fp32
-// elements (V = 1, 2, 4), stream_pass_bf16.hip for bf16 elements (V = 8).
+// elements (V = 1, 2, 4), stream_pass_bf16.hip for bf16 elements (V = 8), and
+// stream_pass_cclip.hip the fp32 STEP pass of centered clipping (the old iterate as column term).
 #include "stream_pass_kernel.h"
 
 namespace gmk {
@@ -89,18 +90,9 @@ static const void* pass_fn_mode(int mode, bool panel) {
   }
 }
 
-// (waves per block, lanes per row segment, rows per thread, blocks per CU) tiles built.
-#define GMK_FOR_EACH_CFG(X_, V_)                                                             \
-  X_(V_, 16, 64, 1, 1) X_(V_, 16, 64, 2, 1) X_(V_, 16, 64, 4, 1) X_(V_, 16, 64, 8, 1)        \
-  X_(V_, 16, 32, 8, 1) X_(V_, 16, 16, 8, 1) X_(V_, 16, 8, 8, 1) X_(V_, 16, 4, 8, 1)          \
-  X_(V_, 16, 4, 4, 1) X_(V_, 16, 16, 4, 1) X_(V_, 8, 8, 16, 1) X_(V_, 8, 4, 8, 1)            \
-  X_(V_, 8, 16, 8, 1) X_(V_, 8, 8, 8, 1) X_(V_, 4, 8, 8, 1) X_(V_, 4, 16, 4, 1)              \
-  X_(V_, 8, 32, 4, 1) X_(V_, 16, 8, 8, 2) X_(V_, 16, 16, 16, 1) X_(V_, 8, 8, 16, 2)          \
-  X_(V_, 8, 32, 4, 4)                                                                        \
-  X_(V_, 16, 32, 8, 2) X_(V_, 16, 64, 4, 2) X_(V_, 16, 64, 16, 1) X_(V_, 8, 16, 8, 2)
-
 static const void* pass_kernel(const PassCfg& cfg, int mode, bool panel = false) {
   if (cfg.B16) return pass_kernel_bf16(cfg, mode, panel);
+  if (mode == kPassStepSelf) return pass_kernel_self(cfg, panel);   // stream_pass_cclip.hip
 #define GMK_CASE(V_, W_, L_, R_, O_)                                                 \
   if (cfg.V == V_ && cfg.NW == W_ && cfg.LPR == L_ && cfg.R == R_ && cfg.OCC == O_) \
     return pass_fn_mode<V_, W_, L_, R_, O_>(mode, panel);

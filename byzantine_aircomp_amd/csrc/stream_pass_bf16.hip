@@ -7,7 +7,8 @@
 // twice as wide (J = LPR * 8), and with it s_red, s_g and the finisher threads.
 //
 // Built: the tiles pick_cfg can return (rows and panels), modes 0 (STEP), 1 (INIT) and
-// 2 (INIT + ||x_k||^2), both layouts, the plain schedule and the rolling prefetch.  Not
+// 2 (INIT + ||x_k||^2) and the STEP pass of centered clipping (SELF: the old iterate as column
+// term), both layouts, the plain schedule and the rolling prefetch.  Not
 // built: the Gram closing sum (mode 3) and the fused OMA write-back (mode 4), which would
 // round the noised values back to bf16.  The 32-wave rows kernel (rows_pass.hip) is never
 // taken: launch_pass selects it for V = 4 tiles only.
@@ -24,17 +25,19 @@ namespace gmk {
 //   the AirComp INIT (mode 2) of tiles with R >= 8  132-184 / 0
 //   the STEP pass of the 256 < K <= 512 tile        20 / 0
 // GMAGG_PASS_VARIANT=0 / 2 forces one schedule.
-template <int NW, int LPR, int R, int OCC, int MODE>
+// SELF: the STEP pass with the old iterate as column term (centered clipping, gm_cclip_bf16;
+// launch mode kPassStepSelf), on the schedule of the plain STEP pass.
+template <int NW, int LPR, int R, int OCC, int MODE, bool SELF = false>
 static const void* pass_fn_bf16(bool panel) {
   const int pv = pass_variant();
   constexpr bool kRollSpills = OCC > 1 || (MODE == 2 && R >= 8) ||
                                (MODE == 0 && LPR == 16 && R == 8);
   const bool roll = pv == 2 || (pv != 0 && (panel || MODE == 0) && !kRollSpills);
   if (panel)
-    return roll ? reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 2, OCC, true, true>)
-                : reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 0, OCC, true, true>);
-  return roll ? reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 2, OCC, false, true>)
-              : reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 0, OCC, false, true>);
+    return roll ? reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 2, OCC, true, true, SELF>)
+                : reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 0, OCC, true, true, SELF>);
+  return roll ? reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 2, OCC, false, true, SELF>)
+              : reinterpret_cast<const void*>(&weiszfeld_pass<8, NW, LPR, R, MODE, 0, OCC, false, true, SELF>);
 }
 
 // pick_cfg's tiles (host_ctx.h): (waves per block, lanes per row segment, rows per thread,
@@ -51,6 +54,7 @@ const void* pass_kernel_bf16(const PassCfg& cfg, int mode, bool panel) {
       case 0: return pass_fn_bf16<W_, L_, R_, O_, 0>(panel);                         \
       case 1: return pass_fn_bf16<W_, L_, R_, O_, 1>(panel);                         \
       case 2: return pass_fn_bf16<W_, L_, R_, O_, 2>(panel);                         \
+      case kPassStepSelf: return pass_fn_bf16<W_, L_, R_, O_, 0, true>(panel);       \
       default: return nullptr;                                                       \
     }                                                                                \
   }

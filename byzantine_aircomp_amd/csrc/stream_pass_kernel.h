@@ -6,6 +6,17 @@
 #include "gmagg_internal.h"
 #include "philox.h"
 
+// (waves per block, lanes per row segment, rows per thread, blocks per CU) fp32 tiles built
+// (stream_pass.hip; stream_pass_cclip.hip builds the same set with SELF).
+#define GMK_FOR_EACH_CFG(X_, V_)                                                             \
+  X_(V_, 16, 64, 1, 1) X_(V_, 16, 64, 2, 1) X_(V_, 16, 64, 4, 1) X_(V_, 16, 64, 8, 1)        \
+  X_(V_, 16, 32, 8, 1) X_(V_, 16, 16, 8, 1) X_(V_, 16, 8, 8, 1) X_(V_, 16, 4, 8, 1)          \
+  X_(V_, 16, 4, 4, 1) X_(V_, 16, 16, 4, 1) X_(V_, 8, 8, 16, 1) X_(V_, 8, 4, 8, 1)            \
+  X_(V_, 8, 16, 8, 1) X_(V_, 8, 8, 8, 1) X_(V_, 4, 8, 8, 1) X_(V_, 4, 16, 4, 1)              \
+  X_(V_, 8, 32, 4, 1) X_(V_, 16, 8, 8, 2) X_(V_, 16, 16, 16, 1) X_(V_, 8, 8, 16, 2)          \
+  X_(V_, 8, 32, 4, 4)                                                                        \
+  X_(V_, 16, 32, 8, 2) X_(V_, 16, 64, 4, 2) X_(V_, 16, 64, 16, 1) X_(V_, 8, 16, 8, 2)
+
 namespace gmk {
 
 // B16: X holds bf16 elements.  The tile stays packed, two adjacent columns per VGPR (the
@@ -34,9 +45,14 @@ struct Tile {
 // it fits the 32-bit lane offset, and the HBM stream is sequential.
 // B16: bf16 elements (a.X is read as uint16_t; ldx / panel_stride count elements), V = 8;
 // modes 0-2 only (mode 4 would round the noised values back to bf16: another algorithm).
+// SELF (STEP only): the column term is the old iterate, g' = sum_k c_k x_k + a_noise * g_old
+// (centered clipping; a.noise is 3 and no draw is added), with phase A's sums in fp64 (see
+// there).  A template parameter, not a fourth runtime kind: gm2 / gm are to run the code
+// they ran before.
 template <int V, int NW, int LPR, int R, int MODE, int SCHED, int OCC = 1, bool PANEL = false,
-          bool B16 = false>
+          bool B16 = false, bool SELF = false>
 __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs a) {
+  static_assert(!SELF || MODE == 0, "the old iterate as column term: STEP passes only");
   constexpr bool PIPE = SCHED == 1, ROLL = SCHED == 2 || SCHED == 3, ROLL2 = SCHED == 3;
   constexpr bool SUM_ONLY = MODE == 3;     // closing pass of the Gram variant: g = sum c_k x_k
   constexpr bool OMA_INIT = MODE == 4;
@@ -52,7 +68,8 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
   static_assert(J <= NW * 64, "one finisher thread per column");
   using T = Tile<V, R, B16>;
 
-  __shared__ float s_red[NW][J];
+  typedef typename std::conditional<SELF, double, float>::type red_t;   // SELF: phase A in fp64
+  __shared__ red_t s_red[NW][J];
   __shared__ float s_g[INIT ? 2 : 1][J];   // INIT: by chunk parity (one barrier per chunk)
   __shared__ double s_fin[2][NW];
   __shared__ float s_w[OCC > 1 ? NW * QW * R : 1];
@@ -244,8 +261,17 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
       par ^= 1;
     } else {
       // phase A: weighted column sums over this thread's rows ...
+      // SELF (centered clipping) sums in fp64, products included: with v' = sum_k c_k x_k + a v
+      // and sum c + a = 1, identical rows x_k = v must give v back, and an fp32 sum of K terms
+      // c_k v is 3-6 ulp off at K = 50-1024 whatever the coefficients are (measured); the
+      // fp64 sum is exact to 2^-53 K and the one rounding left is the final conversion.
       float acc[V];
       f2 accp[B16 ? V / 2 : 1];   // bf16: the column pairs' sums
+      red_t accd[SELF ? V : 1];
+      if constexpr (SELF) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) accd[v] = 0;
+      }
 #pragma unroll
       for (int v = 0; v < V; ++v) acc[v] = 0.f;
 #pragma unroll
@@ -257,11 +283,21 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
         else wi = wt[i];
         if constexpr (B16) {
 #pragma unroll
-          for (int j = 0; j < V / 2; ++j)
-            accp[j] = __builtin_elementwise_fma(f2{wi, wi}, xpair(t, i, j), accp[j]);
+          for (int j = 0; j < V / 2; ++j) {
+            const f2 xv = xpair(t, i, j);
+            if constexpr (SELF) {
+              accd[2 * j] = fma((double)wi, (double)xv[0], accd[2 * j]);
+              accd[2 * j + 1] = fma((double)wi, (double)xv[1], accd[2 * j + 1]);
+            } else {
+              accp[j] = __builtin_elementwise_fma(f2{wi, wi}, xv, accp[j]);
+            }
+          }
         } else {
 #pragma unroll
-          for (int v = 0; v < V; ++v) acc[v] = fmaf(wi, t.x[i][v], acc[v]);
+          for (int v = 0; v < V; ++v) {
+            if constexpr (SELF) accd[v] = fma((double)wi, (double)t.x[i][v], accd[v]);
+            else acc[v] = fmaf(wi, t.x[i][v], acc[v]);
+          }
         }
       }
       if constexpr (B16) {
@@ -272,26 +308,34 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
 #pragma unroll
       for (int o = LPR; o < 64; o <<= 1)
 #pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] += __shfl_xor(acc[v], o, 64);
+        for (int v = 0; v < V; ++v) {
+          if constexpr (SELF) accd[v] += __shfl_xor(accd[v], o, 64);
+          else acc[v] += __shfl_xor(acc[v], o, 64);
+        }
       if (q == 0) {
 #pragma unroll
-        for (int v = 0; v < V; ++v) s_red[w][c * V + v] = acc[v];
+        for (int v = 0; v < V; ++v) {
+          if constexpr (SELF) s_red[w][c * V + v] = accd[v];
+          else s_red[w][c * V + v] = acc[v];
+        }
       }
       __syncthreads();
       // ... and over the waves: one finisher thread per column writes g'.
       if (tid < J) {
-        float sum = 0.f;
+        red_t sum = 0;
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) sum += s_red[ww][tid];
         const int64_t gj = ch * J + tid;
         float gnew = 0.f;
         if (gj < d) {
-          gnew = sum;
+          if constexpr (!SELF) gnew = sum;
           if (a.noise == 1) {
             gnew = fmaf(a_noise, normal1(a.seed, kStreamNoise, a.iter, a.col_off + gj), gnew);
           } else if (a.noise == 2) {
             gnew = fmaf(a_noise, t.hn, gnew);
           }
+          // centered clipping: the old iterate's share a = 1 - sum_k c_k (already here as gold)
+          if constexpr (SELF) gnew = (float)fma((double)a_noise, (double)t.gold, (double)sum);
           a.g_new[gj] = gnew;
           const float diff = t.gold - gnew;
           mv_acc += (double)(diff * diff);

@@ -7,6 +7,8 @@
 //                   stop when ||g - g'|| <= tol, returning g'.
 //   gm   M:131-160  the same step with the weighted sums formed "over the air"
 //                   by OMA2 (M:396-414): channel-inverted gains + AWGN.
+// Beyond the reference: centered clipping (gm_cclip_*), a third K-space rule on the same
+// distances (kModeCclip) whose step is the STEP pass with the old iterate as column term.
 // All per-iteration decisions (weights, tol test) are taken on the device by
 // kspace_step, so the host only polls a `done` word.
 #include "device_util.h"
@@ -118,6 +120,29 @@ __device__ void kspace_body(KspaceArgs& a) {
     return;
   }
 
+  if (a.mode == kModeCclip) {
+    // centered clipping: v' = v + (1/K) sum_k (x_k - v) min(1, tau / ||x_k - v||)
+    //                       = sum_k c_k x_k + a v,  c_k = lambda_k / K,  a = 1 - sum_k c_k.
+    // No distance floor: dist_k = 0 is inside the ball (lambda_k = 1).  a is formed from the
+    // ROUNDED c_k, so sum c + a = 1 up to one rounding and identical rows stay a fixed point.
+    double csum = 0.0, nclip = 0.0;
+    for (int64_t k = tid; k < K; k += blockDim.x) {
+      const double dist = sqrt(D2[k]);
+      const double lam = dist <= a.tau ? 1.0 : a.tau / dist;
+      const float ck = (float)(lam / (double)K);
+      a.coef[k] = ck;
+      csum += (double)ck;
+      nclip += dist > a.tau ? 1.0 : 0.0;
+    }
+    const double C = block_sum(csum, scratch);
+    const double N = block_sum(nclip, scratch);
+    if (tid == 0) {
+      st->a_noise = (float)(1.0 - C);
+      st->clipped = (int32_t)N;
+    }
+    return;
+  }
+
   // gm: the OMA2 weighted sum folded into K-space (SURVEY §3C restatement).
   const int64_t it = a.t + 1;                               // iteration the coefs are for
   const float s = sqrtf((float)(gn2 / (double)a.d_total));  // sqrt(mean(guess^2)) (M:146)
@@ -198,6 +223,7 @@ __global__ void __launch_bounds__(256) twopass_sum(const float* __restrict__ X, 
     for (; k < K; ++k) acc = fmaf(coef[k], X[k * ldx + j], acc);
     if (noise == 1) acc = fmaf(st->a_noise, normal1(seed, kStreamNoise, iter, col_off + j), acc);
     else if (noise == 2) acc = fmaf(st->a_noise, hnoise[j], acc);
+    else if (noise == 3) acc = fmaf(st->a_noise, g_old[j], acc);   // centered clipping
     g_new[j] = acc;
     const float diff = g_old[j] - acc;
     mv += (double)(diff * diff);

@@ -89,7 +89,7 @@ def _aligned(shards, d_total: int) -> bool:
 
 
 class ShardedGM:
-    """gm2 / gm on this rank's column shard of a d_total-long update."""
+    """gm2 / gm / cclip on this rank's column shard of a d_total-long update."""
 
     def __init__(self, d_total: int, group=None, device: torch.device | None = None,
                  transport: str = "rccl", shard: tuple[int, int] | None = None):
@@ -191,6 +191,47 @@ class ShardedGM:
         self.last_result = _result(res)
         if o.pre_oma and X is not X_in:
             X_in.copy_(X)      # the fused pre-noise is in place on the caller's shard
+        return out
+
+    def _operand(self, X):
+        """(X to keep alive, pointer, ldx, layout) of this rank's fp32 [K, d_local] columns."""
+        if X.shape[1] != self.d_local or X.device != self.device or X.dtype != torch.float32:
+            raise ValueError(f"X must be fp32 [K, {self.d_local}] on {self.device}")
+        if isinstance(X, ClientPanels):
+            return X, X.data.data_ptr(), X.panel_stride, _lib.GM_LAYOUT_PANELS
+        if X.stride(1) != 1 or X.data_ptr() % 16 or (X.stride(0) % 4 and X.shape[0] > 1):
+            X = X.clone(memory_format=torch.contiguous_format)
+        return X, X.data_ptr(), max(X.stride(0), self.d_local), _lib.GM_LAYOUT_ROWS
+
+    def cclip(self, X, options):
+        """Centered clipping (aggregators.cclip) on this rank's [K, d_local] columns, fp32 rows
+        or ClientPanels: options ``tau`` (required), ``clip_iters`` (1), ``clip_tol`` (None)
+        and ``guess`` (required: this rank's shard of the starting point), identical on every
+        rank but for the guess's columns.  One all-reduce per pass, as gm2; every rank derives
+        the same coefficients and stop decision.  ``last_result`` holds the trace,
+        ``last_clipped`` the clients outside the radius at the last iteration run."""
+        from .aggregators import _cclip_params
+        options = options or {}
+        tau, iters, tol = _cclip_params(options)
+        guess = options.get("guess")
+        if guess is None:
+            raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
+        X, ptr, ldx, layout = self._operand(X)
+        g0 = guess.to(device=self.device, dtype=torch.float32).contiguous()
+        if g0.numel() != self.d_local:
+            raise ValueError(f"guess has {g0.numel()} elements, this shard has {self.d_local}")
+        out = torch.empty(self.d_local, dtype=torch.float32, device=self.device)
+        o = _lib.GmCclipOpts()
+        o.tau, o.maxiter, o.tol, o.layout = tau, iters, tol, layout
+        res = _lib.GmCclipResult()
+        with torch.cuda.device(self.device):
+            _lib.check(self.ctx.lib.gm_cclip_f32(
+                self.ctx.handle, ptr, X.shape[0], self.d_local, ldx, g0.data_ptr(), out.data_ptr(),
+                C.byref(o), C.byref(res),
+                torch.cuda.current_stream(self.device).cuda_stream), "gm_cclip_f32")
+        self.last_result = GMResult(res.iters, res.last_movement, bool(res.converged),
+                                    "stream" if iters else "none")
+        self.last_clipped = int(res.clipped)
         return out
 
     def gm2(self, X, options=None):

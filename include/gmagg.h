@@ -212,6 +212,44 @@ int gm_weiszfeld_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int6
  * tile's chunk width: 64 columns at 512 < K <= 1024); 0 if K is unsupported. */
 int64_t gm_panel_width_bf16(int64_t K);
 
+/* Centered clipping (Karimireddy, He & Jaggi, "Learning from History for Byzantine Robust
+ * Optimization", ICML 2021, Algorithm 2) — not one of the reference's aggregators.  From
+ * v_0 = guess0, maxiter times
+ *     v_{l+1} = v_l + (1/K) sum_k (x_k - v_l) min(1, tau / ||x_k - v_l||)
+ * computed as sum_k c_k x_k + a v_l on the fused streaming pass: dist_k = sqrt(D_k) in fp64
+ * with no distance floor (dist_k = 0 is unclipped), c_k = (float)(lambda_k / K),
+ * a = (float)(1 - sum_k (double)c_k).  One read of X per iteration, maxiter + 1 in all. */
+typedef struct gm_cclip_opts {
+    double tau;               /* clipping radius, > 0; +inf gives the plain mean step */
+    int64_t maxiter;          /* clipping iterations; 0 copies guess0 to out */
+    double tol;               /* stop early once the fp32 movement ||v_l - v_{l+1}|| <= tol (the
+                                 new iterate is returned); a negative tol never stops */
+    int32_t layout;           /* gm_layout of X */
+    int32_t check_every;      /* host poll interval in iterations; 0 = auto */
+} gm_cclip_opts;
+
+typedef struct gm_cclip_result {
+    int64_t iters;            /* iterations executed */
+    double last_movement;     /* ||v_l - v_{l+1}|| of the last one (NaN if none ran) */
+    int32_t converged;        /* 1 if the loop exited through the tol test */
+    int32_t clipped;          /* clients with dist_k > tau at the last iteration's coefficients */
+} gm_cclip_result;
+
+/* fp32 X, row-major [K][ldx] or panels (gm_panel_width(K), as gm_weiszfeld_f32); K > 2048
+ * row-major runs the two-pass kernels.  Works on a d-sharded context (gm_ctx_set_shard + an
+ * all-reduce) exactly as gm2: every rank derives the same c_k, a and stop decision from the
+ * reduced sums.  gm_ctx_pass_timing counts one pass per iteration.
+ * GM_ERR_INVALID: tau NaN or <= 0 (nothing is written). */
+int gm_cclip_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx,
+                 const float* guess0, float* out, const gm_cclip_opts* opts,
+                 gm_cclip_result* result, void* stream);
+/* bf16 X (bit patterns; layouts and panel width as gm_weiszfeld_bf16), fp32 guess0 / out.
+ * GM_ERR_UNSUPPORTED (with a message) for a sharded or collective context, K > 2048, or a
+ * row-major X that is not 16-byte aligned with d and ldx multiples of 8. */
+int gm_cclip_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                  const float* guess0, float* out, const gm_cclip_opts* opts,
+                  gm_cclip_result* result, void* stream);
+
 /* Batched independent problems (BASELINE config C5, the draw.ipynb-style sweep
  * over many small aggregations): problem p aggregates the K rows at X + p*ldp
  * (row stride ldx) from guess0 + p*ldg into out + p*ldo.  One launch per pass
