@@ -125,6 +125,12 @@ class Context:
                                                C.byref(n)), "gm_ctx_pass_timing")
         return ms.value, n.value
 
+    def call(self, fn: str, *args):
+        """The library's ``fn(handle, *args)`` with this context's device current; GmError on a
+        negative status."""
+        with torch.cuda.device(self.device):
+            return _lib.check(getattr(self.lib, fn)(self.handle, *args), fn)
+
     def close(self):
         """Destroy the context now (workspace, RCCL communicator); idempotent.
         Multi-process callers close before torch.distributed.destroy_process_group()
@@ -190,13 +196,19 @@ def _stage(t: torch.Tensor, bf16_ok: bool = False) -> torch.Tensor:
     return t.to(torch.device("cuda", torch.cuda.current_device()))
 
 
+def _unit_rows(X: torch.Tensor):
+    """(X or a contiguous copy, ldx): unit column stride, rows of the last two dimensions at
+    least d apart."""
+    if X.stride(-1) != 1 or X.stride(-2) < X.shape[-1] or X.shape[-2] == 0:
+        X = X.contiguous()
+    return X, max(X.stride(-2), X.shape[-1])
+
+
 def _rows(X: torch.Tensor):
     """(tensor, ldx) with unit column stride, rows >= d apart."""
     if X.dim() != 2:
         raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
-    if X.stride(1) != 1 or X.stride(0) < X.shape[1] or X.shape[0] == 0:
-        X = X.contiguous()
-    return X, max(X.stride(0), X.shape[1])
+    return _unit_rows(X)
 
 
 def _fp32_panels(p: ClientPanels, who: str) -> ClientPanels:
@@ -267,6 +279,38 @@ def _host_draws(K: int, d: int, noise_var):
     return _lib.NOISE_CB(cb)
 
 
+def _gm_opts(opts: dict, aircomp: bool, layout: int, pre_var=None, pre_seed=None, shape=None):
+    """The library's options from the merged option dict `opts` (maxiter, tol and, for gm,
+    noise_var and P_max are present).  pre_var: the variance of a fused pre-noise, keyed
+    pre_seed.  shape: (K, d_total), for the host draws' callback.  A Philox key that is needed
+    and not given is drawn from the torch CPU generator, one randint each; with
+    ``noise_source="host"`` nothing is drawn here (the callback replays the reference's
+    torch.normal sequence, which an extra draw would shift)."""
+    o = _lib.GmOpts()
+    o.maxiter = int(opts["maxiter"])
+    o.tol = float(opts["tol"])
+    o.eps = 1e-4
+    o.mode = _lib.GM_MODE_AIRCOMP if aircomp else _lib.GM_MODE_IDEAL
+    o.algo = _ALGOS[opts.get("algo", "auto")]
+    o.check_every = int(opts.get("check_every", 0))
+    o.layout = layout
+    if pre_var is not None:
+        o.pre_oma = 1
+        o.pre_oma_var = float(pre_var)
+        o.pre_oma_seed = _seed({"seed": pre_seed})
+    if aircomp:
+        var = opts["noise_var"]
+        o.has_noise = int(var is not None)
+        o.noise_var = float(var) if var is not None else 0.0
+        o.P_max = float(opts["P_max"])
+        o.noise_source = _noise_source(opts)
+        if o.noise_source == _lib.GM_NOISE_HOST:
+            o.noise_cb = o.keep_cb = _host_draws(*shape, var)   # (alive as long as o)
+        else:
+            o.seed = _seed(opts)
+    return o
+
+
 def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
     global last_result
     opts = {"maxiter": 200, "tol": 1e-5}
@@ -307,37 +351,11 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
         last_result = GMResult(1, 0.0, True, "none")
         return out.to(wList.device)
 
-    o = _lib.GmOpts()
-    o.maxiter = maxiter
-    o.tol = float(opts["tol"])
-    o.eps = 1e-4
-    o.mode = _lib.GM_MODE_AIRCOMP if aircomp else _lib.GM_MODE_IDEAL
-    o.algo = _ALGOS[opts.get("algo", "auto")]
-    o.check_every = int(opts.get("check_every", 0))
-    o.layout = layout
-    if pre_var is not None:
-        o.pre_oma = 1
-        o.pre_oma_var = float(pre_var)
-        o.pre_oma_seed = _seed({"seed": pre_seed})
-    cb = None
-    if aircomp:
-        var = opts["noise_var"]
-        o.has_noise = int(var is not None)
-        o.noise_var = float(var) if var is not None else 0.0
-        o.P_max = float(opts["P_max"])
-        o.noise_source = _noise_source(opts)
-        if o.noise_source == _lib.GM_NOISE_HOST:
-            cb = _host_draws(K, d, var)
-            o.noise_cb = cb
-        else:
-            o.seed = _seed(opts)
-    ctx = context(X.device)
+    o = _gm_opts(opts, aircomp, layout, pre_var, pre_seed, (K, d))
     res = _lib.GmResult()
-    fn = "gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32"
-    with torch.cuda.device(X.device):
-        _lib.check(getattr(ctx.lib, fn)(ctx.handle, X.data_ptr(), K, d, ldx, g0.data_ptr(),
-                                        out.data_ptr(), C.byref(o), C.byref(res),
-                                        _stream_ptr(X.device)), fn)
+    context(X.device).call("gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32", X.data_ptr(), K, d,
+                           ldx, g0.data_ptr(), out.data_ptr(), C.byref(o), C.byref(res),
+                           _stream_ptr(X.device))
     last_result = _result(res)
     if pre_var is not None and not isinstance(wList, ClientPanels) and X is not wList:
         # a strided view was packed into a copy: the fused pre-noise landed in the
@@ -379,6 +397,22 @@ def _cclip_params(options):
     return tau, iters, -1.0 if ctol is None else float(ctol)
 
 
+def _run_cclip(ctx, ptr: int, bf16: bool, K: int, d: int, ldx: int, layout: int, g0, params,
+               check_every: int = 0):
+    """gm_cclip_f32 / _bf16 on ctx from the fp32 guess g0 [d], params = _cclip_params(...):
+    (the result [d] on g0's device, the trace, the clients outside the radius at the last
+    iteration run)."""
+    tau, iters, tol = params
+    out = torch.empty(d, dtype=torch.float32, device=g0.device)
+    o = _lib.GmCclipOpts()
+    o.tau, o.maxiter, o.tol, o.layout, o.check_every = tau, iters, tol, layout, check_every
+    res = _lib.GmCclipResult()
+    ctx.call("gm_cclip_bf16" if bf16 else "gm_cclip_f32", ptr, K, d, ldx, g0.data_ptr(),
+             out.data_ptr(), C.byref(o), C.byref(res), _stream_ptr(g0.device))
+    return out, GMResult(res.iters, res.last_movement, bool(res.converged),
+                         "stream" if iters else "none"), int(res.clipped)
+
+
 def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
     """Centered clipping (Karimireddy, He & Jaggi, ICML 2021, Algorithm 2), not one of the
     reference's aggregators: from v = options['guess'] (default the zero vector, as in the
@@ -397,13 +431,13 @@ def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
     outside the radius at the last iteration run."""
     global last_result
     options = options or {}
-    tau, iters, tol = _cclip_params(options)
+    params = _cclip_params(options)
     if not isinstance(wList, ClientPanels) and wList.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"cclip reads fp32 or bf16 client updates (got {wList.dtype})")
     guess = options.get("guess")
     if guess is None:
         guess = torch.zeros(wList.shape[1], dtype=torch.float32, device=wList.device)
-    if iters == 0:
+    if params[1] == 0:
         last_result = GMResult(0, float("nan"), False, "none")
         cclip.last_info = {"clipped": 0}
         return guess
@@ -411,23 +445,14 @@ def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
     g0 = guess.detach().to(device=X.device, dtype=torch.float32).contiguous()
     if g0.numel() != d:
         raise ValueError(f"guess has {g0.numel()} elements, wList rows have {d}")
-    out = torch.empty(d, dtype=torch.float32, device=X.device)
     if d == 0:
         last_result = GMResult(1, 0.0, True, "none")
         cclip.last_info = {"clipped": 0}
-        return out.to(wList.device)
-    o = _lib.GmCclipOpts()
-    o.tau, o.maxiter, o.tol, o.layout = tau, iters, tol, layout
-    o.check_every = int(options.get("check_every", 0))
-    res = _lib.GmCclipResult()
-    ctx = context(X.device)
-    fn = "gm_cclip_bf16" if X.dtype == torch.bfloat16 else "gm_cclip_f32"
-    with torch.cuda.device(X.device):
-        _lib.check(getattr(ctx.lib, fn)(ctx.handle, X.data_ptr(), K, d, ldx, g0.data_ptr(),
-                                        out.data_ptr(), C.byref(o), C.byref(res),
-                                        _stream_ptr(X.device)), fn)
-    last_result = GMResult(res.iters, res.last_movement, bool(res.converged), "stream")
-    cclip.last_info = {"clipped": int(res.clipped)}
+        return torch.empty(d, dtype=torch.float32, device=wList.device)
+    out, last_result, clipped = _run_cclip(
+        context(X.device), X.data_ptr(), X.dtype == torch.bfloat16, K, d, ldx, layout, g0, params,
+        int(options.get("check_every", 0)))
+    cclip.last_info = {"clipped": clipped}
     return out if wList.device == out.device else out.to(wList.device)
 
 
@@ -452,25 +477,21 @@ cclip.with_options = _cclip_with_options
 cclip.last_info = {"clipped": 0}
 
 
+def _fp32_operand(wList, who: str, fn: str):
+    """(tensor, ldx, K, d, function) of an fp32-only aggregator's client matrix: rows (CPU
+    tensors staged) for `fn`, fp32 ClientPanels for its *_panels_f32 twin (same results)."""
+    if isinstance(wList, ClientPanels):
+        _fp32_panels(wList, who)
+        return (wList.data, wList.panel_stride, *wList.shape, fn.replace("_f32", "_panels_f32"))
+    X, ldx = _rows(_stage(wList))
+    return (X, ldx, *X.shape, fn)
+
+
 def _coordinate(wList, fn_name, *extra):
-    if isinstance(wList, ClientPanels):          # the *_panels_f32 kernels (same results)
-        _fp32_panels(wList, fn_name[3:-4])
-        X, ldx, fn_name = wList.data, wList.panel_stride, fn_name.replace("_f32", "_panels_f32")
-        K, d = wList.shape
-        out = torch.empty(d, dtype=torch.float32, device=X.device)
-        ctx = context(X.device)
-        with torch.cuda.device(X.device):
-            _lib.check(getattr(ctx.lib, fn_name)(ctx.handle, X.data_ptr(), K, d, ldx, *extra,
-                                                 out.data_ptr(), _stream_ptr(X.device)), fn_name)
-        return out
-    X = _stage(wList)
-    X, ldx = _rows(X)
-    K, d = X.shape
+    X, ldx, K, d, fn_name = _fp32_operand(wList, fn_name[3:-4], fn_name)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
-    ctx = context(X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(getattr(ctx.lib, fn_name)(ctx.handle, X.data_ptr(), K, d, ldx, *extra,
-                                             out.data_ptr(), _stream_ptr(X.device)), fn_name)
+    context(X.device).call(fn_name, X.data_ptr(), K, d, ldx, *extra, out.data_ptr(),
+                           _stream_ptr(X.device))
     return out if wList.device == out.device else out.to(wList.device)
 
 
@@ -492,22 +513,12 @@ def trimmed_mean(wList, options={}):  # noqa: B006 - reference signature (M:189)
 def Krum(wList, options):  # noqa: N802 - reference name (M:197)
     """The row with the smallest sum of squared distances to its honestSize-1
     nearest rows, itself included (M:197-204)."""
-    if isinstance(wList, ClientPanels):
-        _fp32_panels(wList, "Krum")
-        X, ldx, fn = wList.data, wList.panel_stride, "gm_krum_panels_f32"
-        K, d = wList.shape
-    else:
-        X = _stage(wList)
-        X, ldx = _rows(X)
-        K, d = X.shape
-        fn = "gm_krum_f32"
+    X, ldx, K, d, fn = _fp32_operand(wList, "Krum", "gm_krum_f32")
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     idx = C.c_int64()
     ctx = context(X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(getattr(ctx.lib, fn)(ctx.handle, X.data_ptr(), K, d, ldx,
-                                        int(options["honestSize"]), out.data_ptr(), C.byref(idx),
-                                        _stream_ptr(X.device)), fn)
+    ctx.call(fn, X.data_ptr(), K, d, ldx, int(options["honestSize"]), out.data_ptr(),
+             C.byref(idx), _stream_ptr(X.device))
     info = (C.c_int64 * 3)()
     _lib.check(ctx.lib.gm_krum_last_info(ctx.handle, info), "gm_krum_last_info")
     Krum.last_index = idx.value
@@ -523,24 +534,17 @@ def honest_variance(w_local, honestSize: int) -> torch.Tensor:
     out = torch.empty((), dtype=torch.float32, device=w_local.device)
     if isinstance(w_local, ClientPanels):
         _fp32_panels(w_local, "honest_variance")
-        ctx = context(w_local.device)
-        with torch.cuda.device(w_local.device):
-            _lib.check(ctx.lib.gm_honest_variance_panels_f32(
-                ctx.handle, w_local.data.data_ptr(), w_local.K, int(honestSize), w_local.d,
-                w_local.panel_stride, out.data_ptr(), _stream_ptr(w_local.device)),
-                "gm_honest_variance_panels_f32")
+        context(w_local.device).call(
+            "gm_honest_variance_panels_f32", w_local.data.data_ptr(), w_local.K, int(honestSize),
+            w_local.d, w_local.panel_stride, out.data_ptr(), _stream_ptr(w_local.device))
         return out
     if w_local.device.type != "cuda" or w_local.dtype != torch.float32 or w_local.dim() != 2:
         raise TypeError("honest_variance needs an fp32 CUDA [K, d] matrix or ClientPanels")
-    X = w_local if (w_local.stride(1) == 1 and w_local.stride(0) >= w_local.shape[1]) \
-        else w_local.contiguous()
+    X, ldx = _unit_rows(w_local)
     if not 1 <= honestSize <= X.shape[0]:
         raise ValueError(f"honestSize {honestSize} not in [1, {X.shape[0]}]")
-    ctx = context(X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(ctx.lib.gm_honest_variance_f32(
-            ctx.handle, X.data_ptr(), int(honestSize), X.shape[1], max(X.stride(0), X.shape[1]),
-            out.data_ptr(), _stream_ptr(X.device)), "gm_honest_variance_f32")
+    context(X.device).call("gm_honest_variance_f32", X.data_ptr(), int(honestSize), X.shape[1],
+                           ldx, out.data_ptr(), _stream_ptr(X.device))
     return out
 
 
@@ -554,38 +558,30 @@ def OMA(message, noise_var=0.01, noise_source=None, seed=None):  # noqa: N802 - 
             OMA(rows, noise_var, noise_source=noise_source, seed=seed)
             message.copy_rows_(rows)
             return message
-        ctx = context(message.device)
-        with torch.cuda.device(message.device):
-            _lib.check(ctx.lib.gm_oma_philox_panels_f32(
-                ctx.handle, message.data.data_ptr(), message.K, message.d, message.panel_stride,
-                float(noise_var), _seed({"seed": seed}), _stream_ptr(message.device)),
-                "gm_oma_philox_panels_f32")
+        context(message.device).call(
+            "gm_oma_philox_panels_f32", message.data.data_ptr(), message.K, message.d,
+            message.panel_stride, float(noise_var), _seed({"seed": seed}),
+            _stream_ptr(message.device))
         return message
     if message.dtype != torch.float32:
         raise TypeError(f"OMA kernel is fp32 (got {message.dtype})")
-    X = _stage(message)
-    Xc = X if (X.stride(1) == 1 and X.stride(0) >= X.shape[1]) else X.contiguous()
+    Xc, ldx = _unit_rows(_stage(message))
     K, d = Xc.shape
-    ldx = max(Xc.stride(0), d)
     ctx = context(Xc.device)
     src = _noise_source({} if noise_source is None else {"noise_source": noise_source})
     stream = _stream_ptr(Xc.device)
-    with torch.cuda.device(Xc.device):
-        if src == _lib.GM_NOISE_HOST:
-            sd = math.sqrt(noise_var)
-            hr = torch.normal(torch.zeros(K, 1), 1 / math.sqrt(2))     # M:389-392 order
-            hi = torch.normal(torch.zeros(K, 1), 1 / math.sqrt(2))
-            nr = torch.normal(torch.zeros(K, d), sd)
-            ni = torch.normal(torch.zeros(K, d), sd)
-            dev = [t.to(Xc.device) for t in (hr, hi, nr, ni)]
-            _lib.check(ctx.lib.gm_oma_apply_f32(ctx.handle, Xc.data_ptr(), K, d, ldx,
-                                                *[t.data_ptr() for t in dev], stream),
-                       "gm_oma_apply_f32")
-        else:
-            s = _seed({"seed": seed})
-            _lib.check(ctx.lib.gm_oma_philox_f32(ctx.handle, Xc.data_ptr(), K, d, ldx,
-                                                 float(noise_var), s, stream),
-                       "gm_oma_philox_f32")
+    if src == _lib.GM_NOISE_HOST:
+        sd = math.sqrt(noise_var)
+        hr = torch.normal(torch.zeros(K, 1), 1 / math.sqrt(2))     # M:389-392 order
+        hi = torch.normal(torch.zeros(K, 1), 1 / math.sqrt(2))
+        nr = torch.normal(torch.zeros(K, d), sd)
+        ni = torch.normal(torch.zeros(K, d), sd)
+        dev = [t.to(Xc.device) for t in (hr, hi, nr, ni)]
+        ctx.call("gm_oma_apply_f32", Xc.data_ptr(), K, d, ldx, *[t.data_ptr() for t in dev],
+                 stream)
+    else:
+        ctx.call("gm_oma_philox_f32", Xc.data_ptr(), K, d, ldx, float(noise_var),
+                 _seed({"seed": seed}), stream)
     if Xc is not message:
         message.copy_(Xc)
     return message

@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .aggregators import GMResult, _ALGOS, _result, _seed, _stream_ptr, context
+from .aggregators import _gm_opts, _result, _stream_ptr, _unit_rows, context
 from .panels import panel_width
 
 __all__ = ["gm2_batched", "gm_batched", "oma_batched", "ProblemPanels", "SEED_STRIDE"]
@@ -63,12 +63,9 @@ class ProblemPanels:
         if X.stride(2) != 1:
             X = X.contiguous()
         ctx = context(self.device)
-        with torch.cuda.device(self.device):
-            for p in range(self.P):
-                _lib.check(ctx.lib.gm_rows_to_panels_f32(
-                    ctx.handle, X[p].data_ptr(), self.K, self.d, X.stride(1),
-                    self.data[p].data_ptr(), self.W, self.panel_stride,
-                    _stream_ptr(self.device)), "gm_rows_to_panels_f32")
+        for p in range(self.P):
+            ctx.call("gm_rows_to_panels_f32", X[p].data_ptr(), self.K, self.d, X.stride(1),
+                     self.data[p].data_ptr(), self.W, self.panel_stride, _stream_ptr(self.device))
         return self
 
     @classmethod
@@ -92,10 +89,11 @@ def _run(X, options: dict, aircomp: bool):
             raise ValueError(f"X must be [P, K, d] (got {tuple(X.shape)})")
         if X.device.type != "cuda" or X.dtype != torch.float32:
             raise TypeError("batched aggregation needs an fp32 CUDA tensor")
-        if X.stride(2) != 1 or X.stride(1) < X.shape[2] or X.stride(0) < X.shape[1] * X.stride(1):
-            X = X.contiguous()
+        X, ldx = _unit_rows(X)
+        if X.stride(0) < X.shape[1] * ldx:          # problems that overlap: pack them
+            X, ldx = X.contiguous(), X.shape[2]
         P, K, d = X.shape
-        buf, ldx, ldp = X, X.stride(1), X.stride(0)
+        buf, ldp = X, X.stride(0)
     opts = {"maxiter": 200, "tol": 1e-5, "noise_var": None, "P_max": 1}
     opts.update(options or {})
     # pre_oma_var (gm2): the `--agg gm2 --var v` pre-noise (M:351-352) in place, fused
@@ -115,33 +113,16 @@ def _run(X, options: dict, aircomp: bool):
     if tuple(g0.shape) != (P, d):
         raise ValueError(f"guess must be [P, d] = [{P}, {d}]")
     out = torch.empty(P, d, dtype=torch.float32, device=X.device)
-    o = _lib.GmOpts()
-    o.maxiter = int(opts["maxiter"])
-    o.tol = float(opts["tol"])
-    o.eps = 1e-4
-    o.mode = _lib.GM_MODE_AIRCOMP if aircomp else _lib.GM_MODE_IDEAL
-    o.check_every = int(opts.get("check_every", 0))
-    o.layout = _lib.GM_LAYOUT_PANELS if panels else _lib.GM_LAYOUT_ROWS
-    # "auto" (problems that fit on chip run register-resident, X read once), "stream"
+    # algo: "auto" (problems that fit on chip run register-resident, X read once), "stream"
     # (one streaming pass per iteration over every problem) or "resident" (raises if the
-    # shape does not fit)
-    o.algo = _ALGOS[opts.get("algo", "auto")]
-    if pre_var is not None:
-        o.pre_oma = 1
-        o.pre_oma_var = float(pre_var)
-        o.pre_oma_seed = pre_seed
-    if aircomp:
-        var = opts["noise_var"]
-        o.has_noise = int(var is not None)
-        o.noise_var = float(var) if var is not None else 0.0
-        o.P_max = float(opts["P_max"])
-        o.seed = _seed(opts)
+    # shape does not fit).  AirComp noise is Philox only, whatever noise_source says.
+    opts["noise_source"] = "device"
+    o = _gm_opts(opts, aircomp, _lib.GM_LAYOUT_PANELS if panels else _lib.GM_LAYOUT_ROWS,
+                 pre_var, pre_seed)
     res = (_lib.GmResult * P)()
-    ctx = context(X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(ctx.lib.gm_weiszfeld_batched_f32(
-            ctx.handle, buf.data_ptr(), P, K, d, ldx, ldp, g0.data_ptr(), d,
-            out.data_ptr(), d, C.byref(o), res, _stream_ptr(X.device)), "gm_weiszfeld_batched_f32")
+    context(X.device).call("gm_weiszfeld_batched_f32", buf.data_ptr(), P, K, d, ldx, ldp,
+                           g0.data_ptr(), d, out.data_ptr(), d, C.byref(o), res,
+                           _stream_ptr(X.device))
     if pre_var is not None and X is not X_in:
         X_in.copy_(X)          # the fused pre-noise is in place on the caller's problems
     results = [_result(r) for r in res]
@@ -154,21 +135,17 @@ def oma_batched(X, noise_var: float, seed: int = 2021):
     (M:351-352).  Problem p's draws equal `aggregators.OMA(X[p], noise_var, seed + p *
     SEED_STRIDE)`, in either layout."""
     if isinstance(X, ProblemPanels):
-        ctx = context(X.device)
-        with torch.cuda.device(X.device):
-            _lib.check(ctx.lib.gm_oma_philox_batched_panels_f32(
-                ctx.handle, X.data.data_ptr(), X.P, X.K, X.d, X.panel_stride, X.problem_stride,
-                float(noise_var), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream_ptr(X.device)),
-                "gm_oma_philox_batched_panels_f32")
+        context(X.device).call(
+            "gm_oma_philox_batched_panels_f32", X.data.data_ptr(), X.P, X.K, X.d, X.panel_stride,
+            X.problem_stride, float(noise_var), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            _stream_ptr(X.device))
         return X
     if X.dim() != 3 or X.device.type != "cuda" or X.dtype != torch.float32 or X.stride(2) != 1:
         raise TypeError("oma_batched needs an fp32 CUDA [P, K, d] tensor with unit column stride")
     P, K, d = X.shape
-    ctx = context(X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(ctx.lib.gm_oma_philox_batched_f32(
-            ctx.handle, X.data_ptr(), P, K, d, X.stride(1), X.stride(0), float(noise_var),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, _stream_ptr(X.device)), "gm_oma_philox_batched_f32")
+    context(X.device).call("gm_oma_philox_batched_f32", X.data_ptr(), P, K, d, X.stride(1),
+                           X.stride(0), float(noise_var), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           _stream_ptr(X.device))
     return X
 
 

@@ -56,7 +56,7 @@ int gmh::run_resident_batched(gm_ctx* c, const float* X, int64_t P, int64_t K, i
   a.P_max = o->P_max; a.noise_sd = noise_sd(o);
   a.seed = o->seed;
   a.pre_oma = o->pre_oma ? 1 : 0;
-  a.oma_sd = (float)std::sqrt(std::max(0.0, o->pre_oma_var));
+  a.oma_sd = pre_oma_sd(o);
   a.oma_seed = o->pre_oma_seed;
   a.need = checkin_need(nblocks);
   a.xcd_major = xcd != 0;
@@ -124,16 +124,11 @@ struct BatchedCall {
   hipStream_t s;
 };
 
-// pre_oma (the reference's `--agg gm2 --var v` pre-noise, M:351-352): fused into the
-// INIT pass when the tile takes float4 groups, else the standalone batched OMA first;
-// problem p keyed pre_oma_seed + p * kSeedStride either way
-float pre_oma_sd(const gm_opts* o) { return (float)std::sqrt(std::max(0.0, o->pre_oma_var)); }
-
-int oma_standalone(const BatchedCall& q) {
-  HIPCHK(launch_oma_philox(const_cast<float*>(q.X), q.K, q.d, q.ldx, q.d, 0, pre_oma_sd(q.o),
-                           q.o->pre_oma_seed, q.s, q.panels ? wshift_of(q.Wp) : 0, q.P,
-                           q.P > 1 ? q.ldp : 0));
-  return GM_OK;
+// The call's pre-noise (pre_oma: the reference's `--agg gm2 --var v`, M:351-352), for the
+// paths that do not fuse it into the resident kernel.
+PreOma pre_oma_of(const BatchedCall& q) {
+  return PreOma{q.o->pre_oma != 0, const_cast<float*>(q.X), q.K, q.d, q.ldx, q.d, 0, q.panels,
+                pre_oma_sd(q.o), q.o->pre_oma_seed, q.s, q.P, q.ldp};
 }
 
 // The streaming loop over all problems at once: one INIT pass, then per iteration one STEP
@@ -149,7 +144,6 @@ int run_stream_batched(const BatchedCall& q) {
   if (q.ldp % V) V = 1;
   if (!pick_cfg(K, V, q.ldx, &cfg, q.panels) || (q.panels && cfg.LPR * cfg.V != q.Wp))
     return fail(GM_ERR_UNSUPPORTED, "batched streaming pass supports K <= 2048");
-  const int init_mode = o->mode == GM_MODE_AIRCOMP ? 2 : 1;
   const int J = cfg.LPR * cfg.V;
   const int64_t nch = (d + J - 1) / J;
   // blocks per problem: the grid is OVERSUB rounds of co-resident blocks, so that the
@@ -188,7 +182,7 @@ int run_stream_batched(const BatchedCall& q) {
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(c->ws, 0, zero_end, s));
 
-  KspaceArgs ka = kspace_args(K, d, o);
+  KspaceArgs ka = kspace_args(K, d, o->mode, o->tol, o->eps, air_noise(o));
   ka.noise_src = 0;
   ka.sums = sums;
   ka.r = rr;
@@ -196,37 +190,23 @@ int run_stream_batched(const BatchedCall& q) {
   ka.st = st;
   ka.sums_ps = S;
   ka.n_done = cnt;
-  const int noise_kind = ka.has_noise ? 1 : 0;
 
+  PreOma oma = pre_oma_of(q);
+  StreamPasses sp{c, s};
+  sp.a.X = q.X; sp.a.K = K; sp.a.d = d; sp.a.ldx = q.ldx; sp.a.x_ps = q.ldp;
+  sp.a.gnew_ps = d;
+  sp.a.coef = coef; sp.a.st = st; sp.a.slab = slab;
+  sp.a.noise = ka.has_noise ? 1 : 0; sp.a.seed = o->seed;
+  sp.a.panel_stride = q.panels ? q.ldx : 0;
+  sp.cfg[0] = sp.cfg[1] = cfg;
+  sp.mode[0] = 0; sp.mode[1] = o->mode == GM_MODE_AIRCOMP ? 2 : 1;
+  sp.nb[0] = sp.nb[1] = nbp;
+  sp.problems = (int)P;
+  sp.sums = sums; sp.sums_ps = S;
+  sp.oma = &oma;
   auto do_pass = [&](int64_t t) -> int {
-    const bool init = t < 0;
-    PassArgs a{};
-    a.X = q.X; a.K = K; a.d = d; a.ldx = q.ldx; a.x_ps = q.ldp;
-    if (init || t == 0) { a.g_old = q.guess0; a.gold_ps = q.ldg; }
-    else { a.g_old = g[(t - 1) & 1]; a.gold_ps = d; }
-    a.g_new = init ? nullptr : g[t & 1];
-    a.gnew_ps = d;
-    a.coef = coef; a.st = st; a.slab = slab; a.slab_stride = init ? S : K + 2;
-    a.noise = noise_kind; a.seed = o->seed; a.iter = t;
-    a.panel_stride = q.panels ? q.ldx : 0;
-    int mode = init ? init_mode : 0;
-    if (init && o->pre_oma) {
-      if (cfg.V == 4 && init_mode == 1) {
-        mode = 4;
-        a.oma_sd = pre_oma_sd(o);
-        a.oma_seed = o->pre_oma_seed;
-      } else {
-        const int rco = oma_standalone(q);
-        if (rco) return rco;
-      }
-    }
-    hipEvent_t e0, e1;
-    int rc2 = init ? GM_OK : record_pass_begin(c, s, &e0, &e1);
-    if (rc2) return rc2;
-    HIPCHK(launch_pass(cfg, mode, nbp, a, s, (int)P));
-    if (!init) { rc2 = record_pass_end(c, s, e0, e1); if (rc2) return rc2; }
-    HIPCHK(launch_slab_reduce(slab, nbp, init ? S : K + 2, sums, st, s, (int)P, S));
-    return GM_OK;
+    if (t <= 0) return stream_pass(sp, t, q.guess0, q.ldg, t < 0 ? nullptr : g[0]);
+    return stream_pass(sp, t, g[(t - 1) & 1], d, g[t & 1]);
   };
   int* hcnt = reinterpret_cast<int*>(host_state(c));   // (free until the final copy)
   auto poll_done = [&]() -> int {
@@ -309,10 +289,8 @@ int batched_paths(const BatchedCall& q, bool res_ok) {
     }
   }
   if (o->maxiter == 0) {
-    if (o->pre_oma) {
-      const int rco = oma_standalone(q);
-      if (rco) return rco;
-    }
+    const int rco = pre_oma_of(q).apply();
+    if (rco) return rco;
     HIPCHK(hipMemcpy2DAsync(q.out, q.ldo * 4, q.guess0, q.ldg * 4, d * 4, P,
                             hipMemcpyDeviceToDevice, q.s));
     if (q.results)

@@ -1,7 +1,8 @@
 // Host-only internals of the C-ABI layer, shared by api.hip (context API, thin wrappers,
-// Krum), host_weiszfeld.hip (gm_weiszfeld_f32, gm_weiszfeld_bf16) and host_batched.hip
-// (gm_weiszfeld_batched_f32): the context, error reporting, workspace and pinned-buffer
-// helpers, the all-reduce, pass timing, tile choices and the environment knobs.
+// Krum), host_weiszfeld.hip (gm_weiszfeld_f32, gm_weiszfeld_bf16, gm_cclip_f32, gm_cclip_bf16)
+// and host_batched.hip (gm_weiszfeld_batched_f32): the context, error reporting, workspace
+// and pinned-buffer helpers, the all-reduce, pass timing, tile choices, the environment knobs
+// and the one pass over X that both streaming loops run (stream_pass).
 #pragma once
 #include <rccl/rccl.h>
 
@@ -182,19 +183,33 @@ inline int rb_xcd_major() {
 inline double noise_sd(const gm_opts* o) { return std::sqrt(std::max(0.0, o->noise_var) / 2.0); }
 // whether the AirComp passes add channel noise (options['noise_var'] is not None)
 inline int aircomp_noise(const gm_opts* o) { return o->mode == GM_MODE_AIRCOMP && o->has_noise; }
+// pre_oma's noise std (M:388)
+inline float pre_oma_sd(const gm_opts* o) {
+  return (float)std::sqrt(std::max(0.0, o->pre_oma_var));
+}
+// The AirComp channel fields of a streaming loop (all zero for centered clipping).
+struct AirNoise {
+  int has_noise;
+  double noise_sd, P_max;
+  uint64_t seed;
+};
+inline AirNoise air_noise(const gm_opts* o) {
+  return {aircomp_noise(o), noise_sd(o), o->P_max, o->seed};
+}
 // The K-space step's arguments that come from the options (both streaming loops; the
-// buffers and the per-iteration fields are the caller's)
-inline KspaceArgs kspace_args(int64_t K, int64_t d_total, const gm_opts* o) {
+// buffers and the per-iteration fields are the caller's).  mode: gm_mode, or kModeCclip.
+inline KspaceArgs kspace_args(int64_t K, int64_t d_total, int mode, double tol, double eps,
+                              const AirNoise& n) {
   KspaceArgs ka{};
   ka.K = K;
   ka.d_total = d_total;
-  ka.mode = o->mode;
-  ka.has_noise = aircomp_noise(o);
-  ka.tol = (float)o->tol;
-  ka.eps = (float)o->eps;
-  ka.P_max = o->P_max;
-  ka.noise_sd = noise_sd(o);
-  ka.seed = o->seed;
+  ka.mode = mode;
+  ka.has_noise = n.has_noise;
+  ka.tol = (float)tol;
+  ka.eps = (float)eps;
+  ka.P_max = n.P_max;
+  ka.noise_sd = n.noise_sd;
+  ka.seed = n.seed;
   return ka;
 }
 
@@ -483,6 +498,91 @@ inline bool ensure_stage(gm_ctx* c, size_t bytes) {
   }
   c->stage_bytes = bytes;
   return true;
+}
+
+// ---- one pass of a streaming loop ------------------------------------------------------
+
+// pre_oma: the reference's OMA(weight_f, var) before a non-gm aggregator (M:351-352),
+// applied to X in place, exactly once on whichever path runs.  The streaming loops fuse it
+// into their INIT pass (MODE 4: one read + write of X instead of OMA's read + write and
+// INIT's read); every other path runs the standalone kernel first.  Draws as
+// gm_oma_philox_f32 / _panels_f32; of P batched problems ldp elements apart, problem p is
+// keyed seed + p * kSeedStride either way.
+struct PreOma {
+  bool pending;
+  float* X;
+  int64_t K, d, ldx, d_total, col_off;
+  bool panels;
+  float sd;
+  uint64_t seed;
+  hipStream_t s;
+  int64_t P = 1, ldp = 0;
+  int apply() {
+    if (!pending) return GM_OK;
+    pending = false;
+    const int wshift = panels ? wshift_of(gm_panel_width(K)) : 0;
+    HIPCHK(launch_oma_philox(X, K, d, ldx, d_total, col_off, sd, seed, s, wshift, P,
+                             P > 1 ? ldp : 0));
+    return GM_OK;
+  }
+};
+
+// What the passes of one streaming loop have in common (run_stream, run_stream_batched).
+// The tile, pass mode and grid are indexed by `init`: [0] STEP, [1] INIT.
+struct StreamPasses {
+  gm_ctx* c;
+  hipStream_t s;
+  PassArgs a;        // every field but the iterates, slab_stride, iter, chunk_pair and the OMA's
+  bool twopass;      // the two-pass kernels (one row-major problem) instead of the fused pass
+  PassCfg cfg[2];
+  int mode[2], nb[2];
+  int problems;
+  double* sums;      // the reduced partials, sums_ps apart per problem
+  int64_t sums_ps;
+  bool pair;         // chunk_pair's block order (the single-problem loop on rows)
+  PreOma* oma;
+};
+
+// Pass t over X (t < 0: INIT on the guess; else STEP t from g_old to g_new) and the reduction
+// of its slab into p.sums.  INIT applies a pending pre-noise; STEP passes are the timed ones.
+inline int stream_pass(const StreamPasses& p, int64_t t, const float* g_old, int64_t gold_ps,
+                       float* g_new) {
+  const bool init = t < 0;
+  const PassCfg& cfg = p.cfg[init];
+  const int nb = p.nb[init];
+  int mode = p.mode[init];
+  PassArgs a = p.a;
+  a.g_old = g_old; a.gold_ps = gold_ps; a.g_new = g_new;
+  a.slab_stride = init ? 2 * a.K + 2 : a.K + 2;
+  a.iter = t;
+  a.chunk_pair = p.pair ? chunk_pair(p.c, cfg, nb) : 0;
+  if (init && p.oma->pending) {
+    // the fused OMA needs float4 groups = Philox blocks: a V = 4 tile of the fused pass, the
+    // INIT without the row norms (mode 1), a shard that starts on a multiple of 4 columns
+    // (batched problems are unsharded: col_off = 0)
+    if (!p.twopass && cfg.V == 4 && mode == 1 && a.col_off % 4 == 0) {
+      mode = 4;
+      a.oma_sd = p.oma->sd;
+      a.oma_seed = p.oma->seed;
+      p.oma->pending = false;
+    } else {
+      const int rco = p.oma->apply();
+      if (rco) return rco;
+    }
+  }
+  hipEvent_t e0, e1;
+  int rc = init ? GM_OK : record_pass_begin(p.c, p.s, &e0, &e1);
+  if (rc) return rc;
+  if (p.twopass)   // (reduces its own partials)
+    HIPCHK(launch_twopass(init, a.X, a.K, a.d, a.ldx, g_old, g_new, a.coef, a.st, a.noise,
+                          a.hnoise, a.seed, t, a.col_off, a.slab, nb, p.sums, p.s));
+  else
+    HIPCHK(launch_pass(cfg, mode, nb, a, p.s, p.problems));
+  if (!init) { rc = record_pass_end(p.c, p.s, e0, e1); if (rc) return rc; }
+  if (!p.twopass)
+    HIPCHK(launch_slab_reduce(a.slab, nb, a.slab_stride, p.sums, a.st, p.s, p.problems,
+                              p.sums_ps));
+  return GM_OK;
 }
 
 // Batched problems that fit on chip (host_batched.hip; gm_weiszfeld_f32 runs a panel-layout

@@ -2,7 +2,9 @@
 // validates and selects; the paths are run_gram, run_resident, run_resident_batched with
 // P = 1 (host_batched.hip) and run_stream.  gm_weiszfeld_bf16 (client updates stored as
 // bf16) validates and runs run_stream on a bf16 tile.  gm_cclip_f32 / gm_cclip_bf16 (centered
-// clipping) run the same loop with the clipping rule in the K-space step.
+// clipping) run the same loop with the clipping rule in the K-space step.  What a call asks
+// of run_stream is one StreamJob; the four entry points share one prologue (begin_call,
+// check_panels, no_iteration).
 //
 // The host loop mirrors the reference's control flow (MNIST_Air_weight.py:145-160
 // for gm, 173-184 for gm2) but keeps every decision on the device: the
@@ -27,55 +29,60 @@ struct CallTraits {
   int64_t d_total, col_off;
   bool host_noise;   // AirComp with the caller's draws (GM_NOISE_HOST)
   bool collective;   // sharded, or an all-reduce (RCCL, callback) is set: no resident path
-  double cclip_tau;  // > 0: centered clipping (gm_cclip_*; the options' mode is kModeCclip)
 };
 
-// pre_oma: the reference's OMA(weight_f, var) before a non-gm aggregator (M:351-352),
-// applied to X in place, exactly once on whichever path runs.  The streaming path fuses it
-// into its INIT pass (MODE 4: one read + write of X instead of OMA's read + write and
-// INIT's read); every other path runs the standalone kernel first.  Draws as
-// gm_oma_philox_f32 / _panels_f32.
-struct PreOma {
-  bool pending;
-  float* X;
-  int64_t K, d, ldx, d_total, col_off;
-  bool panels;
-  float sd;
-  uint64_t seed;
+CallTraits traits_of(const gm_ctx* c, int64_t d) {
+  CallTraits tr{};
+  tr.sharded = c->d_total > 0;
+  tr.d_total = tr.sharded ? c->d_total : d;
+  tr.col_off = tr.sharded ? c->d_offset : 0;
+  tr.collective = tr.sharded || c->comm || c->ar_fn;
+  return tr;
+}
+
+// The K-space step's rule: the reference's gm2 and gm (AirComp), or centered clipping.
+enum class Rule { Gm2, Gm, Cclip };
+
+// One call of the launch-per-pass loop (run_stream).
+struct StreamJob {
+  const void* X;         // fp32 elements, or bf16 where the tile says so (cfg.B16)
+  int64_t K, d, ldx;
+  bool panels;           // X in the panel layout, ldx its panel stride, cfg the panel tile
+  PassCfg cfg;           // the STEP tile (two-pass: unused)
+  int algo;              // GM_ALGO_STREAM (the fused pass) or GM_ALGO_TWOPASS
+  const float* guess0;
+  float* out;
+  Rule rule;
+  double tau;            // Rule::Cclip: the clipping radius
+  int64_t maxiter;
+  double tol, eps;
+  int check_every;
+  AirNoise air;          // Rule::Gm
+  gm_noise_cb noise_cb;  // tr.host_noise: the caller's draws
+  void* noise_user;
+  CallTraits tr;
+  PreOma oma;            // the pre-noise still to apply, if any
   hipStream_t s;
-  int apply() {
-    if (!pending) return GM_OK;
-    pending = false;
-    const int wshift = panels ? wshift_of(gm_panel_width(K)) : 0;
-    HIPCHK(launch_oma_philox(X, K, d, ldx, d_total, col_off, sd, seed, s, wshift));
-    return GM_OK;
-  }
-  // The streaming INIT pass: fused into it (mode 4, the pass's own arguments) where the
-  // tile allows, else the standalone kernel first.
-  int fuse_or_apply(bool fusable, PassArgs* a, int* mode) {
-    if (!pending || !fusable) return apply();
-    *mode = 4;
-    a->oma_sd = sd;
-    a->oma_seed = seed;
-    pending = false;
-    return GM_OK;
-  }
+  bool guard_rejected;   // a Gram result was computed and refused before this loop
 };
 
 // The reference's draws of iteration `it` (OMA2, M:401-402, M:411): from the callback
 // into the pinned staging, then to their device copies.
-int upload_draws(gm_ctx* c, const gm_opts* o, const Workspace& w, int64_t K, int64_t d,
-                 const CallTraits& tr, int64_t it, hipStream_t s) {
+int upload_draws(gm_ctx* c, const StreamJob& j, const Workspace& w, int64_t it) {
+  const int64_t K = j.K, d = j.d;
+  hipStream_t s = j.s;
   float* h_hr = host_noise_stage(c);
   float* h_hi = h_hr + K;
   float* h_n = h_hi + K;   // d_total + 1
-  if (o->noise_cb(o->noise_user, it, h_hr, h_hi, o->has_noise ? h_n : nullptr) != 0)
+  if (j.noise_cb(j.noise_user, it, h_hr, h_hi, j.air.has_noise ? h_n : nullptr) != 0)
     return fail(GM_ERR_CALLBACK, "noise callback failed at iteration %lld", (long long)it);
   HIPCHK(hipMemcpyAsync(w.h_re, h_hr, sizeof(float) * K, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(w.h_im, h_hi, sizeof(float) * K, hipMemcpyHostToDevice, s));
-  if (o->has_noise) {
-    HIPCHK(hipMemcpyAsync(w.hnoise, h_n + tr.col_off, sizeof(float) * d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.hnoise + d, h_n + tr.d_total, sizeof(float), hipMemcpyHostToDevice, s));
+  if (j.air.has_noise) {
+    const float* n_cols = h_n + j.tr.col_off;   // this shard's columns, then the last element
+    HIPCHK(hipMemcpyAsync(w.hnoise, n_cols, sizeof(float) * d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.hnoise + d, h_n + j.tr.d_total, sizeof(float), hipMemcpyHostToDevice,
+                          s));
   }
   return GM_OK;
 }
@@ -305,24 +312,32 @@ void stream_grids(const gm_ctx* c, int64_t K, int64_t d, int algo, const PassCfg
 // The launch-per-pass loop: an INIT pass, then per iteration one STEP pass over X (the
 // fused streaming pass on tile cfg, or the two-pass kernels at K > 2048), the all-reduce
 // of its partials and the K-space step.  panels: X in the panel layout, ldx its panel
-// stride, cfg the panel tile (used for INIT too).  oma: the pre-noise still to apply, if
-// any, fused into INIT where the tile allows.
-// Centered clipping (tr.cclip_tau > 0, o->mode = kModeCclip) is the same loop: the K-space
-// step's third rule, and the STEP pass's column term is the old iterate (noise kind 3).
+// stride, cfg the panel tile (used for INIT too).  The job's pre-noise, if any is pending,
+// is fused into INIT where the tile allows.
+// Centered clipping is the same loop: the K-space step's third rule, and the STEP pass's
+// column term is the old iterate.
 // final_state: the KState the result was taken from (nullable).
-int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, const float* guess0,
-               float* out, const gm_opts* o, gm_result* res, const PassCfg& cfg, hipStream_t s,
-               const CallTraits& tr, int algo, bool panels, bool guard_rejected, PreOma* oma,
-               KState* final_state = nullptr) {
-  const bool host_noise = tr.host_noise;
-  const int64_t d_total = tr.d_total, col_off = tr.col_off;
-  const int init_mode = o->mode == GM_MODE_AIRCOMP ? 2 : 1;   // ||x_k||^2 only for AirComp
-  const PassCfg cfg_i = panels ? cfg : light_cfg(K, cfg);
-  int nb_step, nb_init;
-  // centered clipping: the STEP instantiation whose column term is the old iterate
-  const int step_mode = tr.cclip_tau > 0 ? kPassStepSelf : 0;
-  stream_grids(c, K, d, algo, cfg, cfg_i, init_mode, step_mode, &nb_step, &nb_init);
-  const int nb = std::max(nb_step, nb_init);
+int run_stream(gm_ctx* c, StreamJob& j, gm_result* res, KState* final_state = nullptr) {
+  const int64_t K = j.K, d = j.d;
+  hipStream_t s = j.s;
+  const bool host_noise = j.tr.host_noise;
+  const int64_t d_total = j.tr.d_total;
+  const bool cclip = j.rule == Rule::Cclip, air = j.rule == Rule::Gm;
+  // What the rule decides: the INIT pass (||x_k||^2 only for AirComp), the STEP pass and its
+  // column term (PassArgs.noise; clipping's is the old iterate), the K-space step's mode.
+  const int init_mode = air ? 2 : 1;
+  const int step_mode = cclip ? kPassStepSelf : 0;
+  const int noise_kind = cclip ? 3 : !j.air.has_noise ? 0 : (host_noise ? 2 : 1);
+  const int kmode = cclip ? kModeCclip : air ? GM_MODE_AIRCOMP : GM_MODE_IDEAL;
+
+  StreamPasses sp{c, s};
+  sp.twopass = j.algo != GM_ALGO_STREAM;
+  sp.cfg[0] = j.cfg;
+  sp.cfg[1] = j.panels ? j.cfg : light_cfg(K, j.cfg);
+  sp.mode[0] = step_mode;
+  sp.mode[1] = init_mode;
+  stream_grids(c, K, d, j.algo, sp.cfg[0], sp.cfg[1], init_mode, step_mode, &sp.nb[0], &sp.nb[1]);
+  const int nb = std::max(sp.nb[0], sp.nb[1]);
   Workspace w;
   int rc = ensure_ws(c, K, d, nb, &w);
   if (rc) return rc;
@@ -332,9 +347,20 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
   KState* hslot = host_lagged(c);
   HIPCHK(hipMemsetAsync(w.st, 0, sizeof(KState), s));
 
-  const int noise_kind = tr.cclip_tau > 0 ? 3 : !aircomp_noise(o) ? 0 : (host_noise ? 2 : 1);
-  KspaceArgs ka = kspace_args(K, d_total, o);
-  ka.tau = tr.cclip_tau;
+  // (the kernels read a bf16 tile's elements behind the same pointer)
+  sp.a.X = static_cast<const float*>(j.X);
+  sp.a.K = K; sp.a.d = d; sp.a.ldx = j.ldx;
+  sp.a.coef = w.coef; sp.a.st = w.st; sp.a.slab = w.slab;
+  sp.a.noise = noise_kind; sp.a.hnoise = w.hnoise; sp.a.seed = j.air.seed;
+  sp.a.col_off = j.tr.col_off;
+  sp.a.panel_stride = j.panels ? j.ldx : 0;
+  sp.problems = 1;
+  sp.sums = w.sums;
+  sp.pair = !j.panels;
+  sp.oma = &j.oma;
+
+  KspaceArgs ka = kspace_args(K, d_total, kmode, j.tol, j.eps, j.air);
+  ka.tau = j.tau;
   ka.noise_src = host_noise ? 1 : 0;
   ka.sums = w.sums;
   ka.r = w.r;
@@ -352,37 +378,9 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
 
   // Pass over X: INIT (t = -1) or STEP t; leaves the reduced partials in w.sums.
   auto do_pass = [&](int64_t t) -> int {
-    const bool init = t < 0;
-    const float* g_old = init ? guess0 : (t == 0 ? guess0 : w.g[(t - 1) & 1]);
-    float* g_new = init ? nullptr : w.g[t & 1];
-    const int64_t S = init ? 2 * K + 2 : K + 2;
-    hipEvent_t e0, e1;
-    int rc2 = init ? GM_OK : record_pass_begin(c, s, &e0, &e1);
-    if (rc2) return rc2;
-    if (algo == GM_ALGO_STREAM) {
-      PassArgs a{};
-      a.X = X; a.K = K; a.d = d; a.ldx = ldx;
-      a.g_old = g_old; a.g_new = g_new; a.coef = w.coef; a.st = w.st;
-      a.slab = w.slab; a.slab_stride = S;
-      a.noise = noise_kind; a.hnoise = w.hnoise; a.seed = o->seed; a.iter = t; a.col_off = col_off;
-      a.panel_stride = panels ? ldx : 0;
-      a.chunk_pair = panels ? 0 : chunk_pair(c, init ? cfg_i : cfg, init ? nb_init : nb_step);
-      int mode = init ? init_mode : step_mode;
-      if (init) {
-        // the fused OMA needs float4 groups = Philox blocks: V = 4, 4-aligned shards
-        int rco = oma->fuse_or_apply(cfg_i.V == 4 && col_off % 4 == 0 && init_mode == 1, &a, &mode);
-        if (rco) return rco;
-      }
-      HIPCHK(launch_pass(init ? cfg_i : cfg, mode, init ? nb_init : nb_step, a, s));
-      if (!init) { rc2 = record_pass_end(c, s, e0, e1); if (rc2) return rc2; }
-      HIPCHK(launch_slab_reduce(w.slab, init ? nb_init : nb_step, S, w.sums, w.st, s));
-    } else {
-      if (init) { int rco = oma->apply(); if (rco) return rco; }
-      HIPCHK(launch_twopass(init, X, K, d, ldx, g_old, g_new, w.coef, w.st, noise_kind, w.hnoise,
-                            o->seed, t, col_off, w.slab, nb, w.sums, s));
-      if (!init) { rc2 = record_pass_end(c, s, e0, e1); if (rc2) return rc2; }
-    }
-    return allreduce(c, w.sums, S, s);
+    const int rc2 = t <= 0 ? stream_pass(sp, t, j.guess0, 0, t < 0 ? nullptr : w.g[0])
+                           : stream_pass(sp, t, w.g[(t - 1) & 1], 0, w.g[t & 1]);
+    return rc2 ? rc2 : allreduce(c, w.sums, t < 0 ? 2 * K + 2 : K + 2, s);
   };
 
   // Initial distances (and ||x_k||^2, ||g0||^2), then iteration-0 coefficients.
@@ -390,11 +388,11 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
   if (rc) return rc;
   ka.t = -1;
   ka.do_check = 0;
-  if (host_noise) { rc = upload_draws(c, o, w, K, d, tr, 0, s); if (rc) return rc; }
+  if (host_noise) { rc = upload_draws(c, j, w, 0); if (rc) return rc; }
   ka.do_coef = 1;
   HIPCHK(launch_kspace(ka, s));
 
-  int check_every = o->check_every;
+  int check_every = j.check_every;
   if (check_every <= 0) check_every = (K * d_total >= (int64_t)1 << 24) ? 1 : 16;   // global
   if (host_noise) check_every = 1;
   // Polling every iteration (large passes): read iteration t-1's state while
@@ -409,11 +407,11 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
 
   int64_t t = 0, enqueued = 0;
   const KState* final_st = nullptr;   // set when a lagged poll already saw the stop
-  for (; t < o->maxiter; ++t) {
+  for (; t < j.maxiter; ++t) {
     rc = do_pass(t);
     if (rc) return rc;
     enqueued = t + 1;
-    const bool last = t + 1 == o->maxiter;
+    const bool last = t + 1 == j.maxiter;
     ka.t = t;
     if (host_noise) {
       // tol test first; draw the next iteration only if the loop goes on (M:145-159)
@@ -423,7 +421,7 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
       rc = poll(hst);
       if (rc) return rc;
       if (hst->done || last) break;
-      rc = upload_draws(c, o, w, K, d, tr, t + 1, s);
+      rc = upload_draws(c, j, w, t + 1);
       if (rc) return rc;
       ka.do_check = 0;
       ka.do_coef = 1;
@@ -462,32 +460,28 @@ int run_stream(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, con
     if (rc) return rc;
     final_st = hst;
   }
-  gm_result r = result_from(*final_st, algo);
-  r.guard = guard_rejected ? GM_GUARD_REJECTED : GM_GUARD_NONE;
+  gm_result r = result_from(*final_st, j.algo);
+  r.guard = j.guard_rejected ? GM_GUARD_REJECTED : GM_GUARD_NONE;
   if (r.iters < 1) return fail(GM_ERR_HIP, "Weiszfeld loop recorded no iteration");
   // passes queued after the stop (lagged poll) exited at once: not timed as passes
   for (int64_t k = r.iters; k < enqueued; ++k) drop_last_timing(c);
-  HIPCHK(hipMemcpyAsync(out, w.g[(r.iters - 1) & 1], sizeof(float) * d, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(j.out, w.g[(r.iters - 1) & 1], sizeof(float) * d, hipMemcpyDeviceToDevice,
+                        s));
   if (res) *res = r;
   if (final_state) *final_state = *final_st;
   return GM_OK;
 }
 
-// One validated call and what the selection has decided so far.
+// One validated gm_weiszfeld_f32 call and what the selection has decided so far.
 struct Call {
   gm_ctx* c;
   const float* X;
-  int64_t K, d, ldx;
-  const float* guess0;
-  float* out;
+  // The operand, traits and pending pre-noise every path reads, and the streaming loop's job
+  // if the others decline; j.algo is o->algo, narrowed as paths decline
+  StreamJob j;
   const gm_opts* o;
   gm_result* res;
-  hipStream_t s;
-  CallTraits tr;
-  PreOma oma;
   bool res_ok;           // the call's one turn of resident_allowed
-  int algo;              // o->algo, narrowed as paths decline
-  bool guard_rejected;   // a Gram result was computed and refused
 };
 
 // The Gram path on q's X (after the pending pre-noise); a result the guard refuses, or an
@@ -495,12 +489,12 @@ struct Call {
 int try_gram(Call& q, int64_t ldx, const PassCfg& cfg, bool split, bool guarded,
              int64_t pstride = 0) {
   bool rejected = false;
-  int rc = q.oma.apply();
+  int rc = q.j.oma.apply();
   if (rc) return rc;
-  rc = run_gram(q.c, q.X, q.K, q.d, ldx, q.guess0, q.out, q.o, q.res, cfg, q.s, split, guarded,
-                &rejected, pstride);
+  rc = run_gram(q.c, q.X, q.j.K, q.j.d, ldx, q.j.guess0, q.j.out, q.o, q.res, cfg, q.j.s, split,
+                guarded, &rejected, pstride);
   if (rc || !rejected) return rc;
-  q.guard_rejected = true;
+  q.j.guard_rejected = true;
   return kDeclined;
 }
 
@@ -510,29 +504,46 @@ bool panel_cfg(int64_t K, int64_t W, PassCfg* cfg) {
   return W != 0 && pick_cfg(K, 4, W, cfg, true) && cfg->LPR * cfg->V == W;
 }
 
+// What the streaming tile asks of a panel layout [ceil(d/W)][K][W] of `elem`-byte elements:
+// panels at least K*W elements apart, 16-byte aligned (bf16: the panel stride a multiple of
+// 8 elements too), and 32-bit byte offsets within a panel.
+int check_panels(const char* who, const void* X, int64_t K, int64_t W, int64_t ldx, int elem) {
+  if (ldx < K * W || (reinterpret_cast<uintptr_t>(X) & 15) || (elem == 2 && ldx % 8) ||
+      K * W * elem > 0x7fffffff)
+    return fail(GM_ERR_INVALID, "%s: panel layout: need panel stride >= K*W (%lld)%s, 16-byte "
+                "aligned X, K*W*%d < 2^31 (ldx=%lld)", who, (long long)(K * W),
+                elem == 2 ? " and a multiple of 8" : "", elem, (long long)ldx);
+  return GM_OK;
+}
+
+// The fp32 panel tile of a call, and whether its X is laid out for it.
+int f32_panel_tile(const char* who, const float* X, int64_t K, int64_t ldx, PassCfg* cfg) {
+  const int64_t W = gm_panel_width(K);
+  if (!panel_cfg(K, W, cfg))
+    return fail(GM_ERR_UNSUPPORTED, "%s: panel layout: no streaming tile of width %lld for "
+                "K=%lld", who, (long long)W, (long long)K);
+  return check_panels(who, X, K, W, ldx, 4);
+}
+
 // Panels [ceil(d/W)][K][W]: the guarded Gram, the one-XCD resident kernel, the batched
 // resident kernel with P = 1; kDeclined leaves the streaming pass on *cfg.
 int select_panels(Call& q, PassCfg* cfg) {
   gm_ctx* c = q.c;
   const gm_opts* o = q.o;
-  const int64_t K = q.K, d = q.d, ldx = q.ldx;
+  const int64_t K = q.j.K, d = q.j.d, ldx = q.j.ldx;
   const int64_t W = gm_panel_width(K);
-  if (!panel_cfg(K, W, cfg))
-    return fail(GM_ERR_UNSUPPORTED, "panel layout: no streaming tile of width %lld for K=%lld",
-                (long long)W, (long long)K);
-  if (ldx < K * W || (reinterpret_cast<uintptr_t>(q.X) & 15) || K * W * 4 > 0x7fffffff)
-    return fail(GM_ERR_INVALID, "panel layout: need panel stride >= K*W (%lld), 16-byte aligned "
-                "X, K*W*4 < 2^31 (ldx=%lld)", (long long)(K * W), (long long)ldx);
+  const int rcp = f32_panel_tile("gm_weiszfeld_f32", q.X, K, ldx, cfg);
+  if (rcp) return rcp;
   // gm2 at K <= 256: the scaled-f16 Gram reads panels too (AUTO on large d, as
   // for rows, guarded; explicit algo="gram" guarded likewise); streaming otherwise
   const bool gram_ok = o->mode == GM_MODE_IDEAL && gram_kt(K) > 0 && W % 64 == 0 &&
                        (W & (W - 1)) == 0;
-  if ((q.algo == GM_ALGO_AUTO && gram_ok && q.tr.d_total >= (int64_t)1 << 18) ||
-      (q.algo == GM_ALGO_GRAM && gram_ok)) {
+  if ((q.j.algo == GM_ALGO_AUTO && gram_ok && q.j.tr.d_total >= (int64_t)1 << 18) ||
+      (q.j.algo == GM_ALGO_GRAM && gram_ok)) {
     static const bool unguarded = getenv("GMAGG_GRAM_UNGUARDED") != nullptr;
-    const int rc0 = try_gram(q, W, *cfg, true, q.algo == GM_ALGO_AUTO || !unguarded, ldx);
+    const int rc0 = try_gram(q, W, *cfg, true, q.j.algo == GM_ALGO_AUTO || !unguarded, ldx);
     if (rc0 != kDeclined) return rc0;
-    q.algo = GM_ALGO_STREAM;
+    q.j.algo = GM_ALGO_STREAM;
   }
   // One problem that fits on chip: the single-problem resident kernel (C2's, reading the
   // panels with its rows tile: V = 2 columns per lane, within one panel) when its grid
@@ -541,9 +552,9 @@ int select_panels(Call& q, PassCfg* cfg) {
   // K <= 50; the fused pre-noise included).  Either reads the panels once for all
   // iterations.
   auto wants_resident = [&] {
-    return (q.algo == GM_ALGO_AUTO || q.algo == GM_ALGO_RESIDENT) && !q.tr.collective;
+    return (q.j.algo == GM_ALGO_AUTO || q.j.algo == GM_ALGO_RESIDENT) && !q.j.tr.collective;
   };
-  if (wants_resident() && !q.tr.host_noise && K <= 64 && q.res_ok) {
+  if (wants_resident() && !q.j.tr.host_noise && K <= 64 && q.res_ok) {
     PassCfg rcfg{};
     int cpb = 0, nbr = 0;
     if (pick_cfg(K, 2, W, &rcfg) && W % rcfg.V == 0 && (resident_tile(&rcfg, K), true) &&
@@ -551,23 +562,23 @@ int select_panels(Call& q, PassCfg* cfg) {
                       &nbr) &&
         res_xcd_stride(nbr, c->num_cu) == 8) {
       bool timed_out = false;
-      int rco = q.oma.apply();
+      int rco = q.j.oma.apply();
       if (rco) return rco;
-      const int rc0 = run_resident(c, q.X, K, d, K * W, q.guess0, q.out, o, q.res, rcfg, cpb, nbr,
-                                   q.s, &timed_out, ldx, wshift_of(W));
+      const int rc0 = run_resident(c, q.X, K, d, K * W, q.j.guess0, q.j.out, o, q.res, rcfg, cpb,
+                                   nbr, q.j.s, &timed_out, ldx, wshift_of(W));
       if (rc0 || !timed_out) return rc0;
-      q.algo = GM_ALGO_STREAM;   // the X noised above: stream (no second pre-noise)
+      q.j.algo = GM_ALGO_STREAM;   // the X noised above: stream (no second pre-noise)
     }
   }
   if (wants_resident()) {
     const int rc0 = run_resident_batched(c, q.X, 1, K, d, ldx, (d + W - 1) / W * ldx, true, W,
-                                         q.guess0, d, q.out, d, o, q.res, q.s, q.res_ok);
+                                         q.j.guess0, d, q.j.out, d, o, q.res, q.j.s, q.res_ok);
     if (rc0 != kDeclined) return rc0;
   }
-  if (q.algo == GM_ALGO_AUTO) q.algo = GM_ALGO_STREAM;
-  if (q.algo != GM_ALGO_STREAM)
+  if (q.j.algo == GM_ALGO_AUTO) q.j.algo = GM_ALGO_STREAM;
+  if (q.j.algo != GM_ALGO_STREAM)
     return fail(GM_ERR_UNSUPPORTED, "panel layout: streaming, (gm2, K <= 256) Gram or (K <= 52 "
-                "gm2 / K <= 50 gm, unsharded) resident only (algo %d)", q.algo);
+                "gm2 / K <= 50 gm, unsharded) resident only (algo %d)", q.j.algo);
   return kDeclined;
 }
 
@@ -578,12 +589,12 @@ int select_panels(Call& q, PassCfg* cfg) {
 // shard must then meet the kernel's local needs, which shard_range-aligned,
 // contiguous shards of a d_total % 4 == 0 update always do.
 int rows_gram_auto(Call& q, int V) {
-  const int64_t K = q.K, ldx = q.ldx, d_total = q.tr.d_total;
+  const int64_t K = q.j.K, ldx = q.j.ldx, d_total = q.j.tr.d_total;
   PassCfg cfg{};
   const bool local_ok = gram_kt(K) > 0 && V == 4 && ldx < ((int64_t)1 << 26) &&
                         pick_cfg(K, V, ldx, &cfg);
-  const bool take = q.algo == GM_ALGO_AUTO && q.o->mode == GM_MODE_IDEAL && gram_kt(K) > 0 &&
-                    d_total >= (int64_t)1 << 18 && (q.tr.sharded ? d_total % 4 == 0 : local_ok);
+  const bool take = q.j.algo == GM_ALGO_AUTO && q.o->mode == GM_MODE_IDEAL && gram_kt(K) > 0 &&
+                    d_total >= (int64_t)1 << 18 && (q.j.tr.sharded ? d_total % 4 == 0 : local_ok);
   if (!take) return kDeclined;
   if (!local_ok)
     return fail(GM_ERR_INVALID, "sharded gm2 (AUTO -> Gram, d_total=%lld): this rank's shard "
@@ -598,23 +609,23 @@ int rows_gram_auto(Call& q, int V) {
 int rows_resident(Call& q, int V) {
   gm_ctx* c = q.c;
   PassCfg cfg{};
-  if (!((q.algo == GM_ALGO_AUTO || q.algo == GM_ALGO_RESIDENT) && !q.tr.host_noise &&
-        !q.tr.collective && pick_cfg(q.K, V, q.ldx, &cfg)))
+  if (!((q.j.algo == GM_ALGO_AUTO || q.j.algo == GM_ALGO_RESIDENT) && !q.j.tr.host_noise &&
+        !q.j.tr.collective && pick_cfg(q.j.K, V, q.j.ldx, &cfg)))
     return kDeclined;
-  resident_tile(&cfg, q.K);
+  resident_tile(&cfg, q.j.K);
   const int J = cfg.LPR * cfg.V;
-  const int64_t nch = (q.d + J - 1) / J;
+  const int64_t nch = (q.j.d + J - 1) / J;
   int cpb = 0, nbr = 0;
   if (!(q.res_ok && resident_plan(cfg, nch, c->num_cu, &cpb, &nbr))) return kDeclined;
   bool timed_out = false;
-  int rco = q.oma.apply();
+  int rco = q.j.oma.apply();
   if (rco) return rco;
-  const int rc0 = run_resident(c, q.X, q.K, q.d, q.ldx, q.guess0, q.out, q.o, q.res, cfg, cpb, nbr,
-                               q.s, &timed_out);
+  const int rc0 = run_resident(c, q.X, q.j.K, q.j.d, q.j.ldx, q.j.guess0, q.j.out, q.o, q.res, cfg,
+                               cpb, nbr, q.j.s, &timed_out);
   if (rc0 || !timed_out) return rc0;
   // barrier timeout (e.g. a time-sliced GPU): the same problem, same draw keys,
   // on the launch-per-pass streaming path
-  if (q.algo == GM_ALGO_RESIDENT) q.algo = GM_ALGO_AUTO;
+  if (q.j.algo == GM_ALGO_RESIDENT) q.j.algo = GM_ALGO_AUTO;
   return kDeclined;
 }
 
@@ -630,24 +641,29 @@ int rows_resident(Call& q, int V) {
 int rows_staged(Call& q) {
   gm_ctx* c = q.c;
   const gm_opts* o = q.o;
-  const int64_t K = q.K, d = q.d;
-  if (!(q.algo == GM_ALGO_AUTO && aircomp_noise(o) && !q.tr.host_noise && o->maxiter >= 64 &&
-        K * d >= ((int64_t)1 << 24)))
+  const int64_t K = q.j.K, d = q.j.d;
+  if (!(q.j.algo == GM_ALGO_AUTO && aircomp_noise(o) && !q.j.tr.host_noise &&
+        o->maxiter >= 64 && K * d >= ((int64_t)1 << 24)))
     return kDeclined;
   const int64_t W = gm_panel_width(K);
   PassCfg pcfg{};
   if (!stage_enabled() || W <= 0 || K * W * 4 > 0x7fffffff || !panel_cfg(K, W, &pcfg) ||
       !ensure_stage(c, sizeof(float) * (size_t)((d + W - 1) / W) * (size_t)(K * W)))
     return kDeclined;
-  HIPCHK(launch_rows_to_panels(q.X, K, d, q.ldx, c->stage, W, K * W, q.s));
+  HIPCHK(launch_rows_to_panels(q.X, K, d, q.j.ldx, c->stage, W, K * W, q.j.s));
   // (pre_oma is gm2-only, so none is pending on this AirComp call)
-  return run_stream(c, c->stage, K, d, K * W, q.guess0, q.out, o, q.res, pcfg, q.s, q.tr,
-                    GM_ALGO_STREAM, true, q.guard_rejected, &q.oma);
+  StreamJob staged = q.j;
+  staged.X = c->stage;
+  staged.ldx = K * W;
+  staged.panels = true;
+  staged.cfg = pcfg;
+  staged.algo = GM_ALGO_STREAM;
+  return run_stream(c, staged, q.res);
 }
 
 int rows_gram_explicit(Call& q, int V, PassCfg* cfg) {
   const gm_opts* o = q.o;
-  const int64_t K = q.K, d = q.d, ldx = q.ldx;
+  const int64_t K = q.j.K, d = q.j.d, ldx = q.j.ldx;
   if (o->mode != GM_MODE_IDEAL)
     return fail(GM_ERR_UNSUPPORTED, "Gram variant is gm2 only (AirComp noise leaves span(X))");
   if (gram_kt(K) == 0 || V != 4 || !pick_cfg(K, V, ldx, cfg))
@@ -655,54 +671,95 @@ int rows_gram_explicit(Call& q, int V, PassCfg* cfg) {
                 "16-byte aligned X (K=%lld d=%lld ldx=%lld)", (long long)K, (long long)d,
                 (long long)ldx);
   // the split kernel addresses a 16-row group with 32-bit lane offsets
-  const bool split = q.algo == GM_ALGO_GRAM && ldx < ((int64_t)1 << 26);
+  const bool split = q.j.algo == GM_ALGO_GRAM && ldx < ((int64_t)1 << 26);
   // Explicit Gram runs the same a-posteriori guard as AUTO: a result the guard
   // refuses is never returned; the call then runs the streaming path and
   // reports guard = GM_GUARD_REJECTED.  (GMAGG_GRAM_UNGUARDED=1: A/B timing of
   // the bare Gram path, whose closing pass is the lighter sum-only tile.)
   static const bool unguarded = getenv("GMAGG_GRAM_UNGUARDED") != nullptr;
   const int rc0 = try_gram(q, ldx, *cfg, split, !unguarded);
-  if (rc0 == kDeclined) q.algo = GM_ALGO_STREAM;   // pick_cfg(K, V, ldx) succeeded above
+  if (rc0 == kDeclined) q.j.algo = GM_ALGO_STREAM;   // pick_cfg(K, V, ldx) succeeded above
   return rc0;
 }
 
 // Row-major [K][ldx]: try each path in turn and return unless it declined; kDeclined
-// leaves q.algo = GM_ALGO_STREAM on *cfg, or GM_ALGO_TWOPASS (K > 2048).
+// leaves q.j.algo = GM_ALGO_STREAM on *cfg, or GM_ALGO_TWOPASS (K > 2048).
 int select_rows(Call& q, PassCfg* cfg) {
-  const int V = pick_vec(q.X, q.d, q.ldx);
+  const int V = pick_vec(q.X, q.j.d, q.j.ldx);
   int rc = rows_gram_auto(q, V);
   if (rc != kDeclined) return rc;
   rc = rows_resident(q, V);
   if (rc != kDeclined) return rc;
-  if (q.algo == GM_ALGO_RESIDENT)
+  if (q.j.algo == GM_ALGO_RESIDENT)
     return fail(GM_ERR_UNSUPPORTED, "resident kernel: problem too large, sharded or host noise");
   rc = rows_staged(q);
   if (rc != kDeclined) return rc;
-  if (q.algo == GM_ALGO_AUTO || q.algo == GM_ALGO_STREAM) {
-    if (pick_cfg(q.K, V, q.ldx, cfg)) q.algo = GM_ALGO_STREAM;
-    else if (q.algo == GM_ALGO_STREAM)
-      return fail(GM_ERR_UNSUPPORTED, "streaming pass supports K <= 2048 (K=%lld)", (long long)q.K);
-    else q.algo = GM_ALGO_TWOPASS;
+  if (q.j.algo == GM_ALGO_AUTO || q.j.algo == GM_ALGO_STREAM) {
+    if (pick_cfg(q.j.K, V, q.j.ldx, cfg)) q.j.algo = GM_ALGO_STREAM;
+    else if (q.j.algo == GM_ALGO_STREAM)
+      return fail(GM_ERR_UNSUPPORTED, "streaming pass supports K <= 2048 (K=%lld)",
+                  (long long)q.j.K);
+    else q.j.algo = GM_ALGO_TWOPASS;
   }
-  if (q.algo == GM_ALGO_GRAM || q.algo == GM_ALGO_GRAM_F32) {
+  if (q.j.algo == GM_ALGO_GRAM || q.j.algo == GM_ALGO_GRAM_F32) {
     rc = rows_gram_explicit(q, V, cfg);
     if (rc != kDeclined) return rc;
   }
-  if (q.algo != GM_ALGO_STREAM && q.algo != GM_ALGO_TWOPASS)
+  if (q.j.algo != GM_ALGO_STREAM && q.j.algo != GM_ALGO_TWOPASS)
     return fail(GM_ERR_INVALID, "unknown algo %d", q.o->algo);
   return kDeclined;
 }
 
-int validate_call(const gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t ldx,
-                  const float* guess0, const float* out, const gm_opts* o,
-                  const char* who = "gm_weiszfeld_f32") {
-  if (!c || !o || !out || !guess0) return fail(GM_ERR_INVALID, "%s: NULL argument", who);
-  if (K < 1 || d < 1 || (ldx < d && o && o->layout == GM_LAYOUT_ROWS) || (!X)) return fail(GM_ERR_INVALID, "%s: bad shape K=%lld d=%lld ldx=%lld", who, (long long)K, (long long)d, (long long)ldx);
+// ---- the entry points' prologue ----------------------------------------------------------
+
+// What the four entry points check alike (gm_opts and gm_cclip_opts name the layout and the
+// iteration bound alike), then the job's operand, loop controls, traits and stream.
+template <class Opts>
+int begin_call(const char* who, gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t ldx,
+               const float* guess0, float* out, const Opts* o, void* stream, StreamJob* j) {
+  if (!c || !o || !out || !guess0 || !X) return fail(GM_ERR_INVALID, "%s: NULL argument", who);
+  if (o->layout != GM_LAYOUT_ROWS && o->layout != GM_LAYOUT_PANELS)
+    return fail(GM_ERR_INVALID, "%s: unknown layout %d", who, o->layout);
+  if (K < 1 || d < 1 || (ldx < d && o->layout == GM_LAYOUT_ROWS))
+    return fail(GM_ERR_INVALID, "%s: bad shape K=%lld d=%lld ldx=%lld", who, (long long)K,
+                (long long)d, (long long)ldx);
   if (o->maxiter < 0) return fail(GM_ERR_INVALID, "%s: maxiter < 0", who);
+  *j = StreamJob{};
+  j->X = X; j->K = K; j->d = d; j->ldx = ldx;
+  j->panels = o->layout == GM_LAYOUT_PANELS;
+  j->algo = GM_ALGO_STREAM;
+  j->guess0 = guess0;
+  j->out = out;
+  j->maxiter = o->maxiter;
+  j->tol = o->tol;
+  j->check_every = o->check_every;
+  j->tr = traits_of(c, d);
+  j->s = reinterpret_cast<hipStream_t>(stream);
+  return GM_OK;
+}
+
+// gm2 / gm: the rule and the AirComp channel from the options.
+int gm_rule(const char* who, const gm_opts* o, StreamJob* j) {
   if (o->mode != GM_MODE_IDEAL && o->mode != GM_MODE_AIRCOMP)
     return fail(GM_ERR_INVALID, "%s: unknown mode %d", who, o->mode);
   if (o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST && !o->noise_cb)
     return fail(GM_ERR_INVALID, "%s: GM_NOISE_HOST needs noise_cb", who);
+  j->rule = o->mode == GM_MODE_AIRCOMP ? Rule::Gm : Rule::Gm2;
+  j->eps = o->eps;
+  j->air = air_noise(o);
+  j->noise_cb = o->noise_cb;
+  j->noise_user = o->noise_user;
+  j->tr.host_noise = o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST;
+  return GM_OK;
+}
+
+// Centered clipping: the K-space step's third rule (no AirComp draws, INIT without the row
+// norms).
+int cclip_rule(const char* who, const gm_cclip_opts* o, StreamJob* j) {
+  if (!(o->tau > 0.0))   // NaN fails too
+    return fail(GM_ERR_INVALID, "%s: tau must be > 0 (+inf allowed; got %g)", who, o->tau);
+  j->rule = Rule::Cclip;
+  j->tau = o->tau;
   return GM_OK;
 }
 
@@ -713,78 +770,44 @@ int bf16_refuse_collective(const gm_ctx* c, const char* who) {
   return GM_OK;
 }
 
-// The bf16 streaming tile of a call, and whether the kernel can read this X in place.
-int bf16_tile(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, bool panels, PassCfg* cfg,
-              const char* who) {
-  if (!pick_cfg(K, 8, ldx, cfg, panels, true))
+// The bf16 streaming tile of a job, and whether the kernel can read its X in place.
+int bf16_tile(const char* who, StreamJob* j) {
+  const int64_t K = j->K, d = j->d, ldx = j->ldx;
+  if (!pick_cfg(K, 8, ldx, &j->cfg, j->panels, true))
     return fail(GM_ERR_UNSUPPORTED, "%s: no streaming tile for K=%lld (K <= 2048) at ldx=%lld",
                 who, (long long)K, (long long)ldx);
-  const int64_t W = (int64_t)cfg->LPR * cfg->V;
-  const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  if (panels) {
-    if (ldx < K * W || !aligned || ldx % 8 || K * W * 2 > 0x7fffffff)
-      return fail(GM_ERR_INVALID, "%s: panel layout needs panel stride >= K*W (%lld) and a "
-                  "multiple of 8, 16-byte aligned X, K*W*2 < 2^31 (ldx=%lld)", who,
-                  (long long)(K * W), (long long)ldx);
-  } else if (!aligned || ldx % 8 || d % 8) {
+  if (j->panels) return check_panels(who, j->X, K, (int64_t)j->cfg.LPR * j->cfg.V, ldx, 2);
+  if ((reinterpret_cast<uintptr_t>(j->X) & 15) || ldx % 8 || d % 8)
     return fail(GM_ERR_UNSUPPORTED, "%s: row-major bf16 needs 16-byte aligned X with d and ldx "
                 "multiples of 8 (d=%lld ldx=%lld); pack panels (gm_rows_to_panels_bf16)", who,
                 (long long)d, (long long)ldx);
+  return GM_OK;
+}
+
+// maxiter == 0: the loop body never runs and the guess is the result (after the pre-noise,
+// which the reference applies whatever the aggregator then does).
+template <class Res>
+int no_iteration(StreamJob& j, Res* res) {
+  const int rc = j.oma.apply();
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(j.out, j.guess0, sizeof(float) * j.d, hipMemcpyDeviceToDevice, j.s));
+  if (res) {
+    *res = Res{};
+    res->last_movement = NAN;
   }
   return GM_OK;
 }
 
-// maxiter == 0: the loop body never runs and the guess is the result.
-int copy_guess(const float* guess0, float* out, int64_t d, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(out, guess0, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
-  return GM_OK;
-}
-
-// ---- centered clipping -------------------------------------------------------------------
-
-int validate_cclip(const gm_ctx* c, const void* X, int64_t K, int64_t d, int64_t ldx,
-                   const float* guess0, const float* out, const gm_cclip_opts* o, const char* who) {
-  if (!c || !o || !out || !guess0 || !X) return fail(GM_ERR_INVALID, "%s: NULL argument", who);
-  if (o->layout != GM_LAYOUT_ROWS && o->layout != GM_LAYOUT_PANELS)
-    return fail(GM_ERR_INVALID, "%s: unknown layout %d", who, o->layout);
-  if (K < 1 || d < 1 || (ldx < d && o->layout == GM_LAYOUT_ROWS))
-    return fail(GM_ERR_INVALID, "%s: bad shape K=%lld d=%lld ldx=%lld", who, (long long)K,
-                (long long)d, (long long)ldx);
-  if (o->maxiter < 0) return fail(GM_ERR_INVALID, "%s: maxiter < 0", who);
-  if (!(o->tau > 0.0))   // NaN fails too
-    return fail(GM_ERR_INVALID, "%s: tau must be > 0 (+inf allowed; got %g)", who, o->tau);
-  return GM_OK;
-}
-
-// The loop's options for a clipping call: run_stream reads maxiter, tol, check_every and the
-// mode (kModeCclip: no AirComp draws, INIT without the row norms).
-gm_opts cclip_loop_opts(const gm_cclip_opts* o) {
-  gm_opts g{};
-  g.maxiter = o->maxiter;
-  g.tol = o->tol;
-  g.mode = kModeCclip;
-  g.algo = GM_ALGO_STREAM;
-  g.check_every = o->check_every;
-  g.layout = o->layout;
-  return g;
-}
-
-void cclip_result(const gm_result& r, const KState& st, gm_cclip_result* res) {
-  if (!res) return;
+// The clipping loop on a job whose tile is chosen.
+int run_cclip(gm_ctx* c, StreamJob& j, gm_cclip_result* res) {
+  gm_result r{};
+  KState fin{};
+  const int rc = run_stream(c, j, &r, &fin);
+  if (rc || !res) return rc;
   res->iters = r.iters;
   res->last_movement = r.last_movement;
   res->converged = r.converged;
-  res->clipped = st.clipped;
-}
-
-int cclip_no_iteration(const float* guess0, float* out, int64_t d, gm_cclip_result* res,
-                       hipStream_t s) {
-  int rc = copy_guess(guess0, out, d, s);
-  if (rc) return rc;
-  if (res) {
-    *res = gm_cclip_result{};
-    res->last_movement = NAN;
-  }
+  res->clipped = fin.clipped;
   return GM_OK;
 }
 
@@ -798,41 +821,20 @@ extern "C" int gm_cclip_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int
                             const float* guess0, float* out, const gm_cclip_opts* o,
                             gm_cclip_result* res, void* stream) {
   static const char* const who = "gm_cclip_f32";
-  int rc = validate_cclip(c, X, K, d, ldx, guess0, out, o, who);
+  StreamJob j;
+  int rc = begin_call(who, c, X, K, d, ldx, guess0, out, o, stream, &j);
+  if (!rc) rc = cclip_rule(who, o, &j);
   if (rc) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WsOrder order(c, s);
+  WsOrder order(c, j.s);
   HIPCHK(order.err);
-  if (o->maxiter == 0) return cclip_no_iteration(guess0, out, d, res, s);
-  CallTraits tr{};
-  tr.sharded = c->d_total > 0;
-  tr.d_total = tr.sharded ? c->d_total : d;
-  tr.col_off = tr.sharded ? c->d_offset : 0;
-  tr.collective = tr.sharded || c->comm || c->ar_fn;
-  tr.cclip_tau = o->tau;
-  const bool panels = o->layout == GM_LAYOUT_PANELS;
-  PassCfg cfg{};
-  int algo = GM_ALGO_STREAM;
-  if (panels) {
-    const int64_t W = gm_panel_width(K);
-    if (!panel_cfg(K, W, &cfg))
-      return fail(GM_ERR_UNSUPPORTED, "%s: panel layout: no streaming tile of width %lld for "
-                  "K=%lld", who, (long long)W, (long long)K);
-    if (ldx < K * W || (reinterpret_cast<uintptr_t>(X) & 15) || K * W * 4 > 0x7fffffff)
-      return fail(GM_ERR_INVALID, "%s: panel layout: need panel stride >= K*W (%lld), 16-byte "
-                  "aligned X, K*W*4 < 2^31 (ldx=%lld)", who, (long long)(K * W), (long long)ldx);
-  } else if (!pick_cfg(K, pick_vec(X, d, ldx), ldx, &cfg)) {
-    algo = GM_ALGO_TWOPASS;   // K > 2048 (or rows too far apart for the tile's lane offsets)
+  if (j.maxiter == 0) return no_iteration(j, res);
+  if (j.panels) {
+    rc = f32_panel_tile(who, X, K, ldx, &j.cfg);
+    if (rc) return rc;
+  } else if (!pick_cfg(K, pick_vec(X, d, ldx), ldx, &j.cfg)) {
+    j.algo = GM_ALGO_TWOPASS;   // K > 2048 (or rows too far apart for the tile's lane offsets)
   }
-  const gm_opts lo = cclip_loop_opts(o);
-  PreOma none{};
-  gm_result r{};
-  KState fin{};
-  rc = run_stream(c, X, K, d, ldx, guess0, out, &lo, &r, cfg, s, tr, algo, panels, false, &none,
-                  &fin);
-  if (rc) return rc;
-  cclip_result(r, fin, res);
-  return GM_OK;
+  return run_cclip(c, j, res);
 }
 
 // Centered clipping on bf16 client updates: the bf16 instantiation of the fused pass, under
@@ -841,74 +843,46 @@ extern "C" int gm_cclip_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d,
                              const float* guess0, float* out, const gm_cclip_opts* o,
                              gm_cclip_result* res, void* stream) {
   static const char* const who = "gm_cclip_bf16";
-  int rc = validate_cclip(c, X, K, d, ldx, guess0, out, o, who);
+  StreamJob j;
+  int rc = begin_call(who, c, X, K, d, ldx, guess0, out, o, stream, &j);
+  if (!rc) rc = cclip_rule(who, o, &j);
+  if (!rc) rc = bf16_refuse_collective(c, who);
   if (rc) return rc;
-  rc = bf16_refuse_collective(c, who);
-  if (rc) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WsOrder order(c, s);
+  WsOrder order(c, j.s);
   HIPCHK(order.err);
-  if (o->maxiter == 0) return cclip_no_iteration(guess0, out, d, res, s);
-  const bool panels = o->layout == GM_LAYOUT_PANELS;
-  PassCfg cfg{};
-  rc = bf16_tile(X, K, d, ldx, panels, &cfg, who);
+  if (j.maxiter == 0) return no_iteration(j, res);
+  rc = bf16_tile(who, &j);
   if (rc) return rc;
-  CallTraits tr{};
-  tr.d_total = d;
-  tr.cclip_tau = o->tau;
-  const gm_opts lo = cclip_loop_opts(o);
-  PreOma none{};
-  gm_result r{};
-  KState fin{};
-  rc = run_stream(c, reinterpret_cast<const float*>(X), K, d, ldx, guess0, out, &lo, &r, cfg, s,
-                  tr, GM_ALGO_STREAM, panels, false, &none, &fin);
-  if (rc) return rc;
-  cclip_result(r, fin, res);
-  return GM_OK;
+  return run_cclip(c, j, res);
 }
 
 extern "C" int gm_weiszfeld_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
                                 const float* guess0, float* out, const gm_opts* o,
                                 gm_result* res, void* stream) {
-  int rc = validate_call(c, X, K, d, ldx, guess0, out, o);
+  static const char* const who = "gm_weiszfeld_f32";
+  Call q{c, X};
+  StreamJob& j = q.j;
+  int rc = begin_call(who, c, X, K, d, ldx, guess0, out, o, stream, &j);
+  if (!rc) rc = gm_rule(who, o, &j);
   if (rc) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WsOrder order(c, s);
-  HIPCHK(order.err);
-  CallTraits tr{};
-  tr.sharded = c->d_total > 0;
-  tr.d_total = tr.sharded ? c->d_total : d;
-  tr.col_off = tr.sharded ? c->d_offset : 0;
-  tr.host_noise = o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST;
-  tr.collective = tr.sharded || c->comm || c->ar_fn;
   if (o->pre_oma && (o->mode != GM_MODE_IDEAL || !(o->pre_oma_var >= 0)))
     return fail(GM_ERR_INVALID, "pre_oma: gm2 only (the reference applies OMA before non-gm "
                 "aggregators, M:351), noise variance >= 0");
-  const bool panels = o->layout == GM_LAYOUT_PANELS;
-  Call q{c, X, K, d, ldx, guess0, out, o, res, s, tr};
-  q.oma = PreOma{o->pre_oma != 0, const_cast<float*>(X), K, d, ldx, tr.d_total, tr.col_off, panels,
-                 o->pre_oma ? (float)std::sqrt(o->pre_oma_var) : 0.f, o->pre_oma_seed, s};
-  q.algo = o->algo;
-  if (o->maxiter == 0) {
-    rc = q.oma.apply();
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, guess0, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
-    gm_result r{};
-    r.last_movement = NAN;
-    if (res) *res = r;
-    return GM_OK;
-  }
+  WsOrder order(c, j.s);
+  HIPCHK(order.err);
+  q.o = o;
+  q.res = res;
+  j.algo = o->algo;
+  j.oma = PreOma{o->pre_oma != 0, const_cast<float*>(X), K, d, ldx, j.tr.d_total, j.tr.col_off,
+                 j.panels, pre_oma_sd(o), o->pre_oma_seed, j.s};
+  if (j.maxiter == 0) return no_iteration(j, res);
   q.res_ok = o->algo == GM_ALGO_STREAM || resident_allowed(c);
-  if (o->layout != GM_LAYOUT_ROWS && !panels)
-    return fail(GM_ERR_INVALID, "gm_weiszfeld_f32: unknown layout %d", o->layout);
   // Every path that runs returns from the selection; what it declines is left to the
-  // launch-per-pass loop on the tile in cfg (panels keep their own: it sets the chunk
+  // launch-per-pass loop on the tile in j.cfg (panels keep their own: it sets the chunk
   // width the panel layout was built for).
-  PassCfg cfg{};
-  rc = panels ? select_panels(q, &cfg) : select_rows(q, &cfg);
+  rc = j.panels ? select_panels(q, &j.cfg) : select_rows(q, &j.cfg);
   if (rc != kDeclined) return rc;
-  return run_stream(c, X, K, d, ldx, guess0, out, o, res, cfg, s, tr, q.algo, panels,
-                    q.guard_rejected, &q.oma);
+  return run_stream(c, j, res);
 }
 
 // bf16 client updates: the streaming loop only, on the bf16 instantiation of the fused pass
@@ -918,11 +892,10 @@ extern "C" int gm_weiszfeld_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_
                                  const float* guess0, float* out, const gm_opts* o,
                                  gm_result* res, void* stream) {
   static const char* const who = "gm_weiszfeld_bf16";
-  int rc = validate_call(c, X, K, d, ldx, guess0, out, o, who);
+  StreamJob j;
+  int rc = begin_call(who, c, X, K, d, ldx, guess0, out, o, stream, &j);
+  if (!rc) rc = gm_rule(who, o, &j);
   if (rc) return rc;
-  const bool panels = o->layout == GM_LAYOUT_PANELS;
-  if (o->layout != GM_LAYOUT_ROWS && !panels)
-    return fail(GM_ERR_INVALID, "%s: unknown layout %d", who, o->layout);
   if (o->algo != GM_ALGO_AUTO && o->algo != GM_ALGO_STREAM)
     return fail(GM_ERR_UNSUPPORTED, "%s: the streaming pass only (algo %d; the Gram, resident "
                 "and two-pass paths read fp32)", who, o->algo);
@@ -931,24 +904,11 @@ extern "C" int gm_weiszfeld_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_
                 "rounded back to bf16)", who);
   rc = bf16_refuse_collective(c, who);
   if (rc) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WsOrder order(c, s);
+  WsOrder order(c, j.s);
   HIPCHK(order.err);
-  if (o->maxiter == 0) {
-    rc = copy_guess(guess0, out, d, s);
-    if (rc) return rc;
-    gm_result r{};
-    r.last_movement = NAN;
-    if (res) *res = r;
-    return GM_OK;
-  }
-  PassCfg cfg{};
-  rc = bf16_tile(X, K, d, ldx, panels, &cfg, who);
+  if (j.maxiter == 0) return no_iteration(j, res);
+  rc = bf16_tile(who, &j);
   if (rc) return rc;
-  CallTraits tr{};
-  tr.d_total = d;
-  tr.host_noise = o->mode == GM_MODE_AIRCOMP && o->noise_source == GM_NOISE_HOST;
-  PreOma none{};
-  return run_stream(c, reinterpret_cast<const float*>(X), K, d, ldx, guess0, out, o, res, cfg, s,
-                    tr, GM_ALGO_STREAM, panels, false, &none);
+  return run_stream(c, j, res);
 }
+

@@ -95,16 +95,10 @@ class ClientPanels:
                 (torch.bfloat16, torch.bfloat16): "gm_rows_to_panels_bf16"}.get(
                     (X.dtype, self.dtype))
         if X.device.type == "cuda" and pack:
-            from . import _lib
-            from .aggregators import context, _stream_ptr
-            if X.stride(1) != 1 or X.stride(0) < self.d:
-                X = X.contiguous()
-            ctx = context(X.device)
-            with torch.cuda.device(X.device):
-                _lib.check(getattr(ctx.lib, pack)(
-                    ctx.handle, X.data_ptr(), self.K, self.d, max(X.stride(0), self.d),
-                    self.data.data_ptr(), self.W, self.panel_stride, _stream_ptr(X.device)),
-                    pack)
+            from .aggregators import context, _stream_ptr, _unit_rows
+            X, ldx = _unit_rows(X)
+            context(X.device).call(pack, X.data_ptr(), self.K, self.d, ldx, self.data.data_ptr(),
+                                   self.W, self.panel_stride, _stream_ptr(X.device))
             return self
         nf = self._full()
         with torch.no_grad():

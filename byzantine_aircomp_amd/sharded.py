@@ -23,7 +23,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .aggregators import GMResult, Context, _ALGOS, _noise_source, _result, _seed
+from .aggregators import (GMResult, Context, _cclip_params, _gm_opts, _noise_source, _result,
+                          _run_cclip, _stream_ptr)
 from .panels import ClientPanels
 
 __all__ = ["shard_range", "ShardedGM", "torch_allreduce_adapter"]
@@ -139,67 +140,44 @@ class ShardedGM:
     def _run(self, X: torch.Tensor, options: dict, aircomp: bool) -> torch.Tensor:
         opts = {"maxiter": 200, "tol": 1e-5, "noise_var": None, "P_max": 1}
         opts.update(options or {})
-        if X.shape[1] != self.d_local or X.device != self.device or X.dtype != torch.float32:
-            raise ValueError(f"X must be fp32 [K, {self.d_local}] on {self.device}")
+        opts["check_every"] = 0            # (not an option of the sharded calls)
         X_in = X
-        if isinstance(X, ClientPanels):      # this rank's columns in the panel layout
-            ptr, ldx, layout = X.data.data_ptr(), X.panel_stride, _lib.GM_LAYOUT_PANELS
-        else:
-            if X.stride(1) != 1 or X.data_ptr() % 16 or (X.stride(0) % 4 and X.shape[0] > 1):
-                # unit stride and float4-aligned rows, as on every other rank: the AUTO
-                # Gram decision is global, so a rank must never fall short of it locally
-                X = X.clone(memory_format=torch.contiguous_format)
-            ptr, ldx, layout = X.data_ptr(), max(X.stride(0), self.d_local), _lib.GM_LAYOUT_ROWS
-        K = X.shape[0]
+        X, ptr, ldx, layout = self._operand(X)
         guess = opts.get("guess")
         if guess is None:
             raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
         g0 = guess.to(device=self.device, dtype=torch.float32).contiguous()
         out = torch.empty(self.d_local, dtype=torch.float32, device=self.device)
-        o = _lib.GmOpts()
-        o.maxiter = int(opts["maxiter"])
-        o.tol = float(opts["tol"])
-        o.eps = 1e-4
-        o.mode = _lib.GM_MODE_AIRCOMP if aircomp else _lib.GM_MODE_IDEAL
-        o.algo = _ALGOS[opts.get("algo", "auto")]
-        o.layout = layout
-        if not aircomp and opts.get("pre_oma_var") is not None:
-            # OMA pre-noise on this rank's columns (keyed by global column: the shards
-            # together draw what one unsharded OMA would), fused into the first pass
-            if opts.get("pre_oma_seed") is None:
-                raise ValueError("sharded pre-noise needs options['pre_oma_seed'] identical on "
-                                 "every rank")
-            o.pre_oma = 1
-            o.pre_oma_var = float(opts["pre_oma_var"])
-            o.pre_oma_seed = _seed({"seed": opts["pre_oma_seed"]})
+        pre_var = None if aircomp else opts.get("pre_oma_var")
+        # OMA pre-noise on this rank's columns (keyed by global column: the shards
+        # together draw what one unsharded OMA would), fused into the first pass
+        if pre_var is not None and opts.get("pre_oma_seed") is None:
+            raise ValueError("sharded pre-noise needs options['pre_oma_seed'] identical on "
+                             "every rank")
         if aircomp:
-            var = opts["noise_var"]
-            o.has_noise = int(var is not None)
-            o.noise_var = float(var) if var is not None else 0.0
-            o.P_max = float(opts["P_max"])
             if _noise_source(opts) != _lib.GM_NOISE_PHILOX:
                 raise ValueError("sharded AirComp uses on-device Philox noise")
             if opts.get("seed") is None:
                 raise ValueError("sharded AirComp needs options['seed'] identical on every rank")
-            o.seed = _seed(opts)
+        o = _gm_opts(opts, aircomp, layout, pre_var, opts.get("pre_oma_seed"))
         res = _lib.GmResult()
-        with torch.cuda.device(self.device):
-            _lib.check(self.ctx.lib.gm_weiszfeld_f32(
-                self.ctx.handle, ptr, K, self.d_local, ldx,
-                g0.data_ptr(), out.data_ptr(), C.byref(o), C.byref(res),
-                torch.cuda.current_stream(self.device).cuda_stream), "gm_weiszfeld_f32")
+        self.ctx.call("gm_weiszfeld_f32", ptr, X.shape[0], self.d_local, ldx, g0.data_ptr(),
+                      out.data_ptr(), C.byref(o), C.byref(res), _stream_ptr(self.device))
         self.last_result = _result(res)
         if o.pre_oma and X is not X_in:
             X_in.copy_(X)      # the fused pre-noise is in place on the caller's shard
         return out
 
     def _operand(self, X):
-        """(X to keep alive, pointer, ldx, layout) of this rank's fp32 [K, d_local] columns."""
+        """(X to keep alive, pointer, ldx, layout) of this rank's fp32 [K, d_local] columns,
+        as rows or as a ClientPanels."""
         if X.shape[1] != self.d_local or X.device != self.device or X.dtype != torch.float32:
             raise ValueError(f"X must be fp32 [K, {self.d_local}] on {self.device}")
         if isinstance(X, ClientPanels):
             return X, X.data.data_ptr(), X.panel_stride, _lib.GM_LAYOUT_PANELS
         if X.stride(1) != 1 or X.data_ptr() % 16 or (X.stride(0) % 4 and X.shape[0] > 1):
+            # unit stride and float4-aligned rows, as on every other rank: the AUTO
+            # Gram decision is global, so a rank must never fall short of it locally
             X = X.clone(memory_format=torch.contiguous_format)
         return X, X.data_ptr(), max(X.stride(0), self.d_local), _lib.GM_LAYOUT_ROWS
 
@@ -210,9 +188,8 @@ class ShardedGM:
         rank but for the guess's columns.  One all-reduce per pass, as gm2; every rank derives
         the same coefficients and stop decision.  ``last_result`` holds the trace,
         ``last_clipped`` the clients outside the radius at the last iteration run."""
-        from .aggregators import _cclip_params
         options = options or {}
-        tau, iters, tol = _cclip_params(options)
+        params = _cclip_params(options)
         guess = options.get("guess")
         if guess is None:
             raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
@@ -220,18 +197,8 @@ class ShardedGM:
         g0 = guess.to(device=self.device, dtype=torch.float32).contiguous()
         if g0.numel() != self.d_local:
             raise ValueError(f"guess has {g0.numel()} elements, this shard has {self.d_local}")
-        out = torch.empty(self.d_local, dtype=torch.float32, device=self.device)
-        o = _lib.GmCclipOpts()
-        o.tau, o.maxiter, o.tol, o.layout = tau, iters, tol, layout
-        res = _lib.GmCclipResult()
-        with torch.cuda.device(self.device):
-            _lib.check(self.ctx.lib.gm_cclip_f32(
-                self.ctx.handle, ptr, X.shape[0], self.d_local, ldx, g0.data_ptr(), out.data_ptr(),
-                C.byref(o), C.byref(res),
-                torch.cuda.current_stream(self.device).cuda_stream), "gm_cclip_f32")
-        self.last_result = GMResult(res.iters, res.last_movement, bool(res.converged),
-                                    "stream" if iters else "none")
-        self.last_clipped = int(res.clipped)
+        out, self.last_result, self.last_clipped = _run_cclip(
+            self.ctx, ptr, False, X.shape[0], self.d_local, ldx, layout, g0, params)
         return out
 
     def gm2(self, X, options=None):
