@@ -38,6 +38,10 @@ Beyond the reference: ``cclip(wList, options)``, centered clipping (Karimireddy,
 ICML 2021) with the same contract and inputs as ``gm2`` on the same streaming pass; options
 ``tau`` (required), ``clip_iters`` (1), ``clip_tol`` (None), ``guess`` (zeros);
 ``cclip.with_options(tau=...)`` makes an ``aggregate`` for loops that build the dict.
+``bucketing(wList, s)`` is s-bucketing (Karimireddy, He & Jaggi, ICLR 2022): the means of
+random groups of s clients, one HIP pass over fp32 or bf16 rows or panels, fp32 out in either
+layout; ``bucketed(aggregate, s)`` wraps any aggregator above with it (and rescales
+``honestSize``).
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -46,6 +50,7 @@ from __future__ import annotations
 import atexit
 import ctypes as C
 import math
+import operator
 import os
 from dataclasses import dataclass
 
@@ -55,7 +60,7 @@ from . import _lib
 from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
-           "last_result", "Context", "context", "honest_variance"]
+           "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed"]
 
 
 @dataclass
@@ -526,6 +531,146 @@ def Krum(wList, options):  # noqa: N802 - reference name (M:197)
                       "reason": ("ok", "not_chosen", "not_eligible", "gram_nonfinite",
                                  "candidates")[info[2]]}
     return out if wList.device == out.device else out.to(wList.device)
+
+
+def _bucket_size(s) -> int:
+    """s as an int >= 1; ValueError otherwise (a float, a bool, 0, ...)."""
+    try:
+        if isinstance(s, bool):
+            raise TypeError
+        n = operator.index(s)
+    except TypeError:
+        raise ValueError(f"bucketing: s must be an integer >= 1 (got {s!r})") from None
+    if n < 1:
+        raise ValueError(f"bucketing: s must be >= 1 (got {s!r})")
+    return n
+
+
+def _assignment(K: int, s: int, generator=None) -> torch.Tensor:
+    """The random assignment of K clients to ceil(K/s) buckets: ``torch.randperm(K)``, one
+    draw from `generator` (the global CPU generator when None).  Bucket i holds clients
+    ``perm[i*s : (i+1)*s]``."""
+    _bucket_size(s)
+    return torch.randperm(int(K), generator=generator)
+
+
+def _bucket_perm(perm, K: int) -> torch.Tensor:
+    """`perm` as a CPU int64 vector, checked to be a permutation of 0..K-1 (the kernel does
+    not check: a bad index would read outside the matrix)."""
+    p = torch.as_tensor(perm).detach().cpu()
+    if p.dim() != 1 or p.numel() != K or p.dtype.is_floating_point or p.dtype == torch.bool:
+        raise ValueError(f"bucketing: perm must be {K} integers (got {tuple(p.shape)} {p.dtype})")
+    p = p.to(torch.int64)
+    if not torch.equal(torch.sort(p).values, torch.arange(K)):
+        raise ValueError(f"bucketing: perm is not a permutation of 0..{K - 1}")
+    return p
+
+
+def bucketing(wList, s, perm=None, generator=None, layout=None):
+    """s-bucketing (Karimireddy, He & Jaggi, "Byzantine-Robust Learning on Heterogeneous
+    Datasets via Bucketing", ICLR 2022), the pre-step that makes gm2 / gm / cclip / Krum / the
+    coordinate-wise aggregators work on non-iid clients: permute the K clients at random,
+    average each consecutive group of s rows, hand the Kb = ceil(K/s) bucket means to the
+    aggregator.  One memory-bound HIP pass (bucket.hip): K*d elements read, Kb*d floats
+    written, after which every pass of the aggregator reads 1/s of the bytes.
+
+    wList: an fp32 or bf16 [K, d] tensor (any stride or alignment; a CPU tensor is staged to
+    the GPU and the row-major result copied back) or an fp32 or bf16 ClientPanels; never
+    written.  Returns the bucket means as fp32: with ``layout=None`` a [Kb, d] tensor for a
+    tensor and ``ClientPanels(Kb, d)`` (on the GPU) for ClientPanels; ``"rows"`` / ``"panels"``
+    force one.  Each mean is the fp64 sum of its bucket in bucket order, divided by the
+    bucket's size (the last bucket is shorter when s does not divide K) and rounded once, so
+    the values are bit-identical whatever the input or output layout.
+
+    perm: a length-K integer tensor, validated on the host as a permutation of 0..K-1
+    (ValueError) and sent as int32; bucket i is rows ``perm[i*s:(i+1)*s]``.  None:
+    ``bucketing.assignment(K, s, generator)`` = ``torch.randperm(K, generator=generator)``, one
+    draw, from the global CPU generator when no generator is given.  ``bucketing.last_perm``
+    holds the permutation used.  ``s == 1`` returns wList itself: no draw, no launch.
+
+    d-sharded clients (ShardedGM): bucketing is column-local, so each rank buckets its own
+    shard with the SAME perm and hands the result to ``ShardedGM.gm2`` / ``.cclip``."""
+    s = _bucket_size(s)
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"bucketing: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    panels_in = isinstance(wList, ClientPanels)
+    if not panels_in and (not isinstance(wList, torch.Tensor) or wList.dim() != 2):
+        raise ValueError("bucketing: wList must be a [K, d] tensor or ClientPanels")
+    if wList.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"bucketing reads fp32 or bf16 client updates (got {wList.dtype})")
+    if s == 1:
+        return wList
+    K, d = (int(n) for n in wList.shape)
+    if K < 1:
+        raise ValueError("bucketing: wList has no rows")
+    p = _bucket_perm(perm, K) if perm is not None else _assignment(K, s, generator)
+    bucketing.last_perm = p
+    if panels_in:
+        X, ldx, lin = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
+        lin = _lib.GM_LAYOUT_ROWS
+    Kb = -(-K // s)
+    if layout == "panels" or (layout is None and panels_in):
+        out = ClientPanels(Kb, d, device=X.device, zero=False)   # every column < d is written
+        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        out = Y = torch.empty(Kb, d, dtype=torch.float32, device=X.device)
+        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    if d > 0:
+        # (pdev goes back to torch's caching allocator, which reuses it in stream order)
+        pdev = p.to(device=X.device, dtype=torch.int32)
+        context(X.device).call(
+            "gm_bucket_means_bf16" if X.dtype == torch.bfloat16 else "gm_bucket_means_f32",
+            X.data_ptr(), K, d, ldx, lin, pdev.data_ptr(), s, Y.data_ptr(), ldy, lout,
+            _stream_ptr(X.device))
+    if out is Y and wList.device != Y.device:
+        return Y.to(wList.device)
+    return out
+
+
+bucketing.assignment = _assignment
+bucketing.last_perm = None
+
+
+def bucketed(aggregate, s, generator=None, layout="panels"):
+    """An ``aggregate(wList, options)`` callable that s-buckets wList (``bucketing``, a fresh
+    random assignment from `generator` per call) and calls `aggregate` on the bucket means,
+    handed over in `layout` ("panels", the layout the streaming pass reads fastest, "rows",
+    or None for wList's own).  Named ``f"{aggregate.__name__}_b{s}"``; works with gm2, gm,
+    ``cclip.with_options(...)``, mean, median, trimmed_mean and Krum, and as
+    ``training.run(..., aggregate=bucketed(gm2, 2))``.
+
+    Options pass through unchanged except ``honestSize``: with B = K - honestSize Byzantine
+    clients at most B buckets are contaminated, so the inner call gets
+    ``honestSize' = ceil(K/s) - B`` (ValueError if that is < 2: s is too large for this many
+    Byzantine clients).  The caller's dict is not modified.  ``s == 1`` calls `aggregate`
+    directly.  The result lives on wList.device, as the aggregators' own."""
+    s = _bucket_size(s)
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"bucketed: layout must be None, 'rows' or 'panels' (got {layout!r})")
+
+    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+        if s == 1:
+            return aggregate(wList, options)
+        K = int(wList.shape[0])
+        Kb = -(-K // s)
+        opts = options
+        if options and options.get("honestSize") is not None:
+            inner = Kb - (K - int(options["honestSize"]))
+            if inner < 2:
+                raise ValueError(
+                    f"{agg.__name__}: {K - int(options['honestSize'])} Byzantine clients leave "
+                    f"honestSize' = {inner} of {Kb} buckets (needs >= 2): use a smaller s")
+            opts = dict(options, honestSize=inner)
+        out = aggregate(bucketing(wList, s, generator=generator, layout=layout), opts)
+        if isinstance(out, torch.Tensor) and out.device != wList.device:
+            out = out.to(wList.device)        # (a CPU wList's means stayed on the GPU as panels)
+        return out
+
+    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_b{s}"
+    agg.__doc__ = f"{aggregate.__name__} on the bucket means of s = {s} bucketing"
+    return agg
 
 
 def honest_variance(w_local, honestSize: int) -> torch.Tensor:

@@ -1,5 +1,5 @@
 // C ABI of libgmagg.so (include/gmagg.h): contexts, the coordinate-wise aggregators, Krum's
-// host side, OMA, the synthetic fills, the panel pack and the client chain.  The Weiszfeld
+// host side, OMA, the synthetic fills, the panel pack, s-bucketing and the client chain.  The Weiszfeld
 // entry points are in host_weiszfeld.hip and host_batched.hip; what the three share is in
 // host_ctx.h.
 #include <cstring>
@@ -464,6 +464,54 @@ int gm_rows_to_panels_bf16_from_f32(gm_ctx* c, const float* X, int64_t K, int64_
 int gm_rows_to_panels_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
                            uint16_t* P, int64_t W, int64_t panel_stride, void* stream) {
   return pack_bf16(c, X, false, K, d, ldx, P, W, panel_stride, stream, "gm_rows_to_panels_bf16");
+}
+
+// s-bucketing of validated pointers: the layouts' panel widths (0 for rows) and strides
+static int bucket_means(const char* fn, gm_ctx* c, const void* X, bool bf16, int64_t K, int64_t d,
+                        int64_t ldx, int32_t lin, const int32_t* perm, int64_t s, float* Y,
+                        int64_t ldy, int32_t lout, void* stream) {
+  auto known = [](int32_t l) { return l == GM_LAYOUT_ROWS || l == GM_LAYOUT_PANELS; };
+  if (!c || !X || !Y || K < 1 || d < 0 || s < 1 || !known(lin) || !known(lout))
+    return fail(GM_ERR_INVALID, "%s: bad args (a NULL ctx, X or Y, K < 1, d < 0, s < 1 or an "
+                "unknown layout)", fn);
+  const int64_t Kb = s >= K ? 1 : (K + s - 1) / s;
+  int64_t Wi = 0, Wo = 0;
+  if (lin == GM_LAYOUT_PANELS) {
+    Wi = bf16 ? gm_panel_width_bf16(K) : gm_panel_width(K);
+    if (Wi == 0)
+      return fail(GM_ERR_UNSUPPORTED, "%s: no panel layout for K = %lld input rows (pass them "
+                  "row-major)", fn, (long long)K);
+  } else if (K > 0x7fffffffll) {
+    return fail(GM_ERR_INVALID, "%s: K = %lld exceeds the int32 row indices", fn, (long long)K);
+  }
+  if (lout == GM_LAYOUT_PANELS) {
+    Wo = gm_panel_width(Kb);
+    if (Wo == 0)
+      return fail(GM_ERR_UNSUPPORTED, "%s: no panel layout for the %lld bucket means (take them "
+                  "row-major)", fn, (long long)Kb);
+  }
+  if (ldx < (Wi ? K * Wi : d) || ldy < (Wo ? Kb * Wo : d))
+    return fail(GM_ERR_INVALID, "%s: ldx = %lld or ldy = %lld too small for its layout", fn,
+                (long long)ldx, (long long)ldy);
+  if (d == 0) return GM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(launch_bucket_means(X, bf16, K, d, ldx, Wi, perm, s, Y, ldy, Wo,
+                             reinterpret_cast<hipStream_t>(stream)));
+  return GM_OK;
+}
+
+int gm_bucket_means_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
+                        int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
+                        int32_t layout_out, void* stream) {
+  return bucket_means("gm_bucket_means_f32", c, X, false, K, d, ldx, layout_in, perm, s, Y, ldy,
+                      layout_out, stream);
+}
+
+int gm_bucket_means_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
+                         int32_t layout_out, void* stream) {
+  return bucket_means("gm_bucket_means_bf16", c, X, true, K, d, ldx, layout_in, perm, s, Y, ldy,
+                      layout_out, stream);
 }
 
 int gm_client_chain_f32(gm_ctx* c, const float* data, int64_t ldd, const int64_t* labels,

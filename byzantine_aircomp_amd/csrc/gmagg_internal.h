@@ -340,6 +340,14 @@ hipError_t launch_rows_to_panels(const float* X, int64_t K, int64_t d, int64_t l
 hipError_t launch_rows_to_panels_bf16(const void* X, bool src_f32, int64_t K, int64_t d,
                                       int64_t ldx, uint16_t* P, int64_t W, int64_t pstride,
                                       hipStream_t s);
+// s-bucketing (bucket.hip): Y[i] = the fp64 mean, rounded once, of rows perm[i s] ...
+// perm[min(K, (i + 1) s) - 1] of X (perm == nullptr: the identity), i < ceil(K / s).  X fp32 or
+// bf16 bit patterns, row-major [K][ldx] (Wi = 0) or panels of width Wi with panel stride
+// ldx; Y fp32 rows [ceil(K/s)][ldy] (Wo = 0) or panels of width Wo with panel stride ldy.
+// Any alignment (4-column vector items where both sides allow, else one column per item).
+hipError_t launch_bucket_means(const void* X, bool bf16, int64_t K, int64_t d, int64_t ldx,
+                               int64_t Wi, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
+                               int64_t Wo, hipStream_t stream);
 hipError_t launch_oma_philox(float* X, int64_t K, int64_t d, int64_t ldx, int64_t d_total,
                              int64_t col_off, float sd, uint64_t seed, hipStream_t s,
                              int wshift = 0, int64_t problems = 1, int64_t pstride = 0);

@@ -13,8 +13,10 @@ row-major call (same chunks, same reduction order).
 
 ``ClientPanels(..., dtype=torch.bfloat16)`` stores the values as bf16 in the layout of
 ``gm_weiszfeld_bf16`` (W = ``gm_panel_width_bf16(K)``): half the bytes per streaming pass.
-``gm2`` / ``gm`` read them widened to fp32 (exact) and return fp32; the other aggregators
-take fp32 panels only.
+``gm2`` / ``gm`` / ``cclip`` read them widened to fp32 (exact) and return fp32; the other
+aggregators take fp32 panels only.  ``bucketing`` (s-bucketing, aggregators.py) reads fp32 and
+bf16 panels alike and writes its fp32 bucket means as ``ClientPanels(ceil(K/s), d)``, whose
+panel width is that of the smaller K.
 """
 from __future__ import annotations
 
@@ -39,15 +41,22 @@ def panel_width(K: int, dtype=torch.float32) -> int:
 class ClientPanels:
     """K client vectors of length d, stored as ``data[ceil(d/W), K, W]`` fp32 or bf16."""
 
-    def __init__(self, K: int, d: int, device=None, W: int | None = None, dtype=torch.float32):
+    def __init__(self, K: int, d: int, device=None, W: int | None = None, dtype=torch.float32,
+                 zero: bool = True):
         if dtype not in _DTYPES:
             raise TypeError(f"ClientPanels holds fp32 or bf16 (got {dtype})")
         self.K, self.d = int(K), int(d)
         self.W = int(W) if W is not None else panel_width(K, dtype)
         self.npan = -(-self.d // self.W)
         dev = torch.device(device) if device is not None else torch.device("cuda")
-        # zero-filled: the last panel's columns >= d stay 0
-        self.data = torch.zeros(self.npan, self.K, self.W, dtype=dtype, device=dev)
+        # zero-filled: the last panel's columns >= d stay 0.  zero=False (a producer that
+        # writes every column < d, e.g. bucketing) zeroes that padding only
+        if zero:
+            self.data = torch.zeros(self.npan, self.K, self.W, dtype=dtype, device=dev)
+        else:
+            self.data = torch.empty(self.npan, self.K, self.W, dtype=dtype, device=dev)
+            if self.npan and self.d % self.W:
+                self.data[-1, :, self.d % self.W:] = 0
 
     # -- shape / metadata, so callers can treat it like the [K, d] matrix --------
     @property

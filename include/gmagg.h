@@ -355,6 +355,35 @@ int gm_rows_to_panels_bf16_from_f32(gm_ctx* ctx, const float* X, int64_t K, int6
 int gm_rows_to_panels_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
                            uint16_t* P, int64_t W, int64_t panel_stride, void* stream);
 
+/* s-bucketing (Karimireddy, He & Jaggi, "Byzantine-Robust Learning on Heterogeneous Datasets
+ * via Bucketing", ICLR 2022), the pre-step of every aggregator above on non-iid clients:
+ *     Y[i] = mean of rows perm[i*s] .. perm[min(K, (i+1)*s) - 1] of X,   i < Kb = ceil(K / s)
+ * (the last bucket is shorter when s does not divide K; s >= K gives one bucket).  Each
+ * element is the fp64 sum of its bucket in that order, divided by the bucket's row count and
+ * rounded to fp32 once; NaN and infinities propagate by IEEE rules.  The order is fixed, so the
+ * result is bit-identical for every input layout, output layout and alignment.
+ *   perm   device int32[K], or NULL for the identity.  It MUST be a permutation of 0..K-1:
+ *          the kernel does not check it, and an entry outside [0, K) reads out of bounds.
+ *   X      fp32 (gm_bucket_means_f32) or bfloat16 bit patterns (gm_bucket_means_bf16, widened
+ *          exactly), layout_in GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any alignment, K < 2^31)
+ *          or GM_LAYOUT_PANELS ([ceil(d/W)][K][W], W = gm_panel_width(K) resp.
+ *          gm_panel_width_bf16(K), ldx = panel stride >= K*W).  Never written.
+ *   Y      fp32, layout_out GM_LAYOUT_ROWS ([Kb][ldy], ldy >= d) or GM_LAYOUT_PANELS
+ *          ([ceil(d/Wo)][Kb][Wo], Wo = gm_panel_width(Kb), ldy = panel stride >= Kb*Wo;
+ *          padding columns >= d of the last panel are not written).
+ * One stream-ordered kernel that reads K*d elements and writes Kb*d floats: no workspace, no
+ * host synchronisation.  GM_ERR_INVALID (nothing written): a NULL ctx, X or Y, K < 1, d < 0,
+ * s < 1, an unknown layout, ldx or ldy too small for its layout.  GM_ERR_UNSUPPORTED (with a
+ * message): panel input whose K, or panel output whose Kb, has no panel width.  d == 0
+ * returns GM_OK.  Bucketing is column-local: on a d-sharded matrix every rank buckets its own
+ * columns with the same perm. */
+int gm_bucket_means_f32 (gm_ctx* ctx, const float*    X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
+                         int32_t layout_out, void* stream);
+int gm_bucket_means_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
+                         int32_t layout_out, void* stream);
+
 /* The K clients' local SGD steps of one federated step (the loop body M:291-343:
  * forward, CrossEntropyLoss (mean), backward, p -= gamma * (grad + weight_decay * p),
  * the client's parameters copied out as its row), as one stream-ordered kernel, for the
