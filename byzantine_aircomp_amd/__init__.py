@@ -8,8 +8,8 @@ HIP kernels for gfx950 behind a C ABI (include/gmagg.h, libgmagg.so):
 See DESIGN.md for the kernels and INTEGRATION.md for swapping them into the
 reference's training loop.
 """
-from .aggregators import (GMResult, Krum, OMA, bucketed, bucketing, cclip, context,  # noqa: F401
-                          gm, gm2, mean, median, trimmed_mean)
+from .aggregators import (GMResult, Krum, OMA, bucketed, bucketing, bulyan, cclip,  # noqa: F401
+                          context, gm, gm2, meamed, mean, median, multi_krum, trimmed_mean)
 from .panels import ClientPanels, panel_width  # noqa: F401
 
 __version__ = "0.1.0"

@@ -42,6 +42,12 @@ ICML 2021) with the same contract and inputs as ``gm2`` on the same streaming pa
 random groups of s clients, one HIP pass over fp32 or bf16 rows or panels, fp32 out in either
 layout; ``bucketed(aggregate, s)`` wraps any aggregator above with it (and rescales
 ``honestSize``).
+``multi_krum(wList, options)`` (Blanchard et al. 2017: the mean of the ``m`` best Krum-scored
+rows), ``bulyan(wList, options)`` (El Mhamdi, Guerraoui & Rouault 2018: recursive Krum
+selection, then a mean around the median) and ``meamed(wList, options)`` (Xie, Koyejo & Gupta
+2018: per coordinate the mean of the ``honestSize`` values nearest to the median) take fp32
+rows or panels and ``honestSize`` like ``Krum``; they work under ``bucketed`` and as a
+training loop's ``aggregate``.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -60,7 +66,8 @@ from . import _lib
 from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
-           "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed"]
+           "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
+           "multi_krum", "bulyan", "meamed"]
 
 
 @dataclass
@@ -533,6 +540,121 @@ def Krum(wList, options):  # noqa: N802 - reference name (M:197)
     return out if wList.device == out.device else out.to(wList.device)
 
 
+def _robust_operand(wList, who: str):
+    """(tensor, ldx, layout, K, d) of the client matrix of meamed / multi_krum / bulyan: an
+    fp32 [K, d] tensor (a CPU tensor staged) or fp32 ClientPanels.  Call _robust_shape first:
+    it refuses other inputs before anything touches a GPU."""
+    if isinstance(wList, ClientPanels):
+        _fp32_panels(wList, who)
+        return (wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS, *wList.shape)
+    X, ldx = _rows(_stage(wList))
+    return (X, ldx, _lib.GM_LAYOUT_ROWS, *X.shape)
+
+
+def _robust_shape(wList, who: str):
+    """(K, d) of an fp32 [K, d] tensor or fp32 ClientPanels; TypeError for another dtype (bf16
+    is read by gm2 / gm / cclip / bucketing only), ValueError for another shape."""
+    if isinstance(wList, ClientPanels):
+        _fp32_panels(wList, who)
+    elif not isinstance(wList, torch.Tensor) or wList.dtype != torch.float32:
+        raise TypeError(f"{who} is fp32 only (got {getattr(wList, 'dtype', type(wList))})")
+    elif wList.dim() != 2:
+        raise ValueError(f"wList must be [K, d] (got {tuple(wList.shape)})")
+    K, d = (int(n) for n in wList.shape)
+    if K < 1:
+        raise ValueError(f"{who}: wList has no rows")
+    return K, d
+
+
+def _honest_size(options, who: str) -> int:
+    if not options or options.get("honestSize") is None:
+        raise ValueError(f"{who} needs options['honestSize']")
+    return int(options["honestSize"])
+
+
+def meamed(wList, options):
+    """Mean-around-median (Xie, Koyejo & Gupta 2018), not one of the reference's aggregators:
+    per coordinate, the mean of the ``honestSize`` values nearest to the coordinate's lower
+    median (ties at the threshold to the lower row index; fp64 sum, rounded once; a NaN in
+    the column gives NaN).  One HIP pass that reads wList once (robust.hip col_meamed).
+    wList: an fp32 [K, d] tensor or fp32 ClientPanels, K <= 1024, 1 <= honestSize <= K; the
+    result is fp32 on wList.device."""
+    K, d = _robust_shape(wList, "meamed")
+    keep = _honest_size(options, "meamed")
+    if not 1 <= keep <= K:
+        raise ValueError(f"meamed: honestSize {keep} not in [1, {K}]")
+    if K > 1024:
+        raise ValueError(f"meamed: K <= 1024 (got {K})")
+    X, ldx, layout, K, d = _robust_operand(wList, "meamed")
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    context(X.device).call("gm_meamed_f32", X.data_ptr(), K, d, ldx, layout, None, K, keep,
+                           out.data_ptr(), _stream_ptr(X.device))
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+def multi_krum(wList, options):
+    """Multi-Krum (Blanchard et al., NeurIPS 2017): the mean of the ``options['m']`` (default
+    honestSize) rows of smallest Krum score, ties to the lower row index; each coordinate is
+    the fp64 sum of the selected rows in increasing row index, divided by m, rounded once.
+    The scores are Krum's on the exact distance path (GMAGG_KRUM is ignored); ``m == 1`` is
+    that Krum row bit for bit.  wList: an fp32 [K, d] tensor or fp32 ClientPanels, K <= 4096,
+    2 <= honestSize <= K + 1, 1 <= m <= K.  ``multi_krum.last_selected`` holds the selected
+    rows, increasing."""
+    K, d = _robust_shape(wList, "multi_krum")
+    honest = _honest_size(options, "multi_krum")
+    if not 2 <= honest <= K + 1:
+        raise ValueError(f"multi_krum: honestSize {honest} not in [2, {K + 1}]")
+    m = options.get("m")
+    m = honest if m is None else int(m)
+    if not 1 <= m <= K:
+        raise ValueError(f"multi_krum: m = {m} not in [1, {K}]")
+    if K > 4096:
+        raise ValueError(f"multi_krum: K <= 4096 (got {K})")
+    X, ldx, layout, K, d = _robust_operand(wList, "multi_krum")
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    sel = (C.c_int32 * m)()
+    if d > 0:
+        context(X.device).call("gm_multi_krum_f32", X.data_ptr(), K, d, ldx, layout, honest, m,
+                               out.data_ptr(), sel, _stream_ptr(X.device))
+    multi_krum.last_selected = list(sel) if d > 0 else []
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+multi_krum.last_selected = None
+
+
+def bulyan(wList, options):
+    """Bulyan (El Mhamdi, Guerraoui & Rouault, ICML 2018) with f = K - honestSize Byzantine
+    rows, K >= 4f + 3: theta = K - 2f rounds of Krum selection on the rows that remain (a
+    row's score: the sum of its max(1, |S| - f - 1) smallest squared distances within the
+    remaining set S, itself included; the smallest score, ties to the lower index, is selected
+    and leaves S; the distances are computed once), then mean-around-median over the selected
+    rows keeping theta - 2f values per coordinate (f == 0: the column mean).  wList: an fp32
+    [K, d] tensor or fp32 ClientPanels, K <= 1024.  ``bulyan.last_selected`` holds the
+    selected rows in selection order."""
+    K, d = _robust_shape(wList, "bulyan")
+    honest = _honest_size(options, "bulyan")
+    f = K - honest
+    if honest < 1 or f < 0:
+        raise ValueError(f"bulyan: honestSize {honest} not in [1, {K}]")
+    if K < 4 * f + 3:
+        raise ValueError(f"bulyan: K = {K} < 4f + 3 = {4 * f + 3} with f = K - honestSize = {f}")
+    if K > 1024:
+        raise ValueError(f"bulyan: K <= 1024 (got {K})")
+    X, ldx, layout, K, d = _robust_operand(wList, "bulyan")
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    theta = K - 2 * f
+    sel = (C.c_int32 * theta)()
+    if d > 0:
+        context(X.device).call("gm_bulyan_f32", X.data_ptr(), K, d, ldx, layout, honest,
+                               out.data_ptr(), sel, _stream_ptr(X.device))
+    bulyan.last_selected = list(sel) if d > 0 else []
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+bulyan.last_selected = None
+
+
 def _bucket_size(s) -> int:
     """s as an int >= 1; ValueError otherwise (a float, a bool, 0, ...)."""
     try:
@@ -638,7 +760,8 @@ def bucketed(aggregate, s, generator=None, layout="panels"):
     random assignment from `generator` per call) and calls `aggregate` on the bucket means,
     handed over in `layout` ("panels", the layout the streaming pass reads fastest, "rows",
     or None for wList's own).  Named ``f"{aggregate.__name__}_b{s}"``; works with gm2, gm,
-    ``cclip.with_options(...)``, mean, median, trimmed_mean and Krum, and as
+    ``cclip.with_options(...)``, mean, median, trimmed_mean, Krum, multi_krum, bulyan and meamed,
+    and as
     ``training.run(..., aggregate=bucketed(gm2, 2))``.
 
     Options pass through unchanged except ``honestSize``: with B = K - honestSize Byzantine

@@ -1,5 +1,5 @@
 // C ABI of libgmagg.so (include/gmagg.h): contexts, the coordinate-wise aggregators, Krum's
-// host side, OMA, the synthetic fills, the panel pack, s-bucketing and the client chain.  The Weiszfeld
+// host side, MeaMed / Multi-Krum / Bulyan, OMA, the synthetic fills, the panel pack, s-bucketing and the client chain.  The Weiszfeld
 // entry points are in host_weiszfeld.hip and host_batched.hip; what the three share is in
 // host_ctx.h.
 #include <cstring>
@@ -372,6 +372,119 @@ static int krum_impl(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ld
     HIPCHK(hipStreamSynchronize(s));
   }
   return GM_OK;
+}
+
+// ---- MeaMed, Multi-Krum, Bulyan (robust.hip) ------------------------------------------------
+
+// The panel shift of a validated layout (0 for rows) after the stride check.
+static int robust_shift(const char* fn, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                        int* ws) {
+  *ws = 0;
+  if (layout == GM_LAYOUT_ROWS) {
+    if (ldx < d) return fail(GM_ERR_INVALID, "%s: ldx = %lld < d", fn, (long long)ldx);
+    return GM_OK;
+  }
+  const int64_t W = gm_panel_width(K);
+  if (W == 0)
+    return fail(GM_ERR_UNSUPPORTED, "%s: no panel layout for K = %lld rows (pass them row-major)",
+                fn, (long long)K);
+  if (ldx < K * W)
+    return fail(GM_ERR_INVALID, "%s: panel stride %lld < K * W = %lld", fn, (long long)ldx,
+                (long long)(K * W));
+  *ws = wshift_of(W);
+  return GM_OK;
+}
+
+static bool known_layout(int32_t l) { return l == GM_LAYOUT_ROWS || l == GM_LAYOUT_PANELS; }
+
+int gm_meamed_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                  const int32_t* rows, int64_t n_rows, int64_t keep, float* out, void* stream) {
+  if (!c || !X || !out || K < 1 || d < 0 || !known_layout(layout) || n_rows < 1 || n_rows > K ||
+      (!rows && n_rows != K) || keep < 1 || keep > n_rows)
+    return fail(GM_ERR_INVALID, "gm_meamed_f32: bad args (a NULL ctx, X or out, K < 1, d < 0, an "
+                "unknown layout, n_rows outside [1, K] or != K without rows, keep outside "
+                "[1, n_rows])");
+  if (K > 1024) return fail(GM_ERR_UNSUPPORTED, "gm_meamed_f32: K <= 1024 (got %lld)", (long long)K);
+  int ws = 0;
+  const int rc = robust_shift("gm_meamed_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(launch_meamed(X, d, ldx, ws, rows, n_rows, keep, out,
+                       reinterpret_cast<hipStream_t>(stream)));
+  return GM_OK;
+}
+
+// The exact path's distances into w->G (Krum's workspace layout: the slices' partials in the
+// float slab); int32 scratch: w->u holds 2K, w->r 2K.
+static int krum_distances(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                          Workspace* w, hipStream_t s) {
+  const size_t part_doubles = (size_t)krum_slices(K, d) * (size_t)(K * K);
+  const int rc = ensure_ws(c, K, 1, 1, w, 2 * part_doubles, (int)K);
+  if (rc) return rc;
+  HIPCHK(launch_krum_dist(X, K, d, ldx, ws, w->G, reinterpret_cast<double*>(w->gslab), s));
+  return GM_OK;
+}
+
+static int copy_selected(int32_t* selected, const int32_t* dev, int64_t n, hipStream_t s) {
+  if (!selected) return GM_OK;
+  HIPCHK(hipMemcpyAsync(selected, dev, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return GM_OK;
+}
+
+int gm_multi_krum_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                      int64_t honest, int64_t m, float* out, int32_t* selected, void* stream) {
+  if (!c || !X || !out || K < 1 || d < 0 || !known_layout(layout) || honest < 2 ||
+      honest - 1 > K || m < 1 || m > K)
+    return fail(GM_ERR_INVALID, "gm_multi_krum_f32: bad args (a NULL ctx, X or out, K < 1, d < 0, "
+                "an unknown layout; needs 2 <= honestSize <= K+1 and 1 <= m <= K)");
+  if (K > 4096)
+    return fail(GM_ERR_UNSUPPORTED, "gm_multi_krum_f32: K <= 4096 (got %lld)", (long long)K);
+  int ws = 0;
+  int rc = robust_shift("gm_multi_krum_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  Workspace w;
+  rc = krum_distances(c, X, K, d, ldx, ws, &w, s);
+  if (rc) return rc;
+  HIPCHK(launch_krum_scores(w.G, K, honest - 1, w.alpha, s));
+  int32_t* flag = reinterpret_cast<int32_t*>(w.u);
+  int32_t* list = flag + K;
+  HIPCHK(launch_multi_krum_pick(w.alpha, K, m, X, d, ldx, ws, flag, list, out, s));
+  return copy_selected(selected, list, m, s);
+}
+
+int gm_bulyan_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                  int64_t honest, float* out, int32_t* selected, void* stream) {
+  const int64_t f = K - honest;
+  if (!c || !X || !out || K < 1 || d < 0 || !known_layout(layout) || honest < 1 || f < 0 ||
+      K < 4 * f + 3)
+    return fail(GM_ERR_INVALID, "gm_bulyan_f32: bad args (a NULL ctx, X or out, K < 1, d < 0, an "
+                "unknown layout; needs f = K - honestSize >= 0 and K >= 4f + 3)");
+  if (K > 1024) return fail(GM_ERR_UNSUPPORTED, "gm_bulyan_f32: K <= 1024 (got %lld)", (long long)K);
+  int ws = 0;
+  int rc = robust_shift("gm_bulyan_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  const int64_t theta = K - 2 * f, beta = theta - 2 * f;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  Workspace w;
+  rc = krum_distances(c, X, K, d, ldx, ws, &w, s);
+  if (rc) return rc;
+  int32_t* alive = reinterpret_cast<int32_t*>(w.u);
+  int32_t* list = alive + K;
+  int32_t* picked = reinterpret_cast<int32_t*>(w.r);
+  // (the slices' partials are dead once D is reduced: the float slab holds >= 2 K^2 words)
+  int32_t* ord = reinterpret_cast<int32_t*>(w.gslab);
+  HIPCHK(launch_bulyan_select(w.G, K, f, theta, w.alpha, ord, alive, picked, list, s));
+  HIPCHK(launch_meamed(X, d, ldx, ws, list, theta, beta, out, s));
+  return copy_selected(selected, picked, theta, s);
 }
 
 int gm_oma_philox_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, double noise_var,

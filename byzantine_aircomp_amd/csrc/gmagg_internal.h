@@ -292,6 +292,28 @@ int64_t krum_slices(int64_t K, int64_t d);
 hipError_t launch_krum(const float* X, int64_t K, int64_t d, int64_t ldx, int64_t kk, double* D,
                        double* part, double* score, float* out, int64_t* index, hipStream_t s,
                        int ws = 0);
+// launch_krum's first two steps on their own: D (pair_dist + pair_reduce), and every row's
+// score (the sum of its kk smallest distances).
+hipError_t launch_krum_dist(const float* X, int64_t K, int64_t d, int64_t ldx, int ws, double* D,
+                            double* part, hipStream_t s);
+hipError_t launch_krum_scores(const double* D, int64_t K, int64_t kk, double* score,
+                              hipStream_t s);
+// MeaMed, Multi-Krum and Bulyan (robust.hip).
+// The mean of the `keep` values of each column nearest to its lower median, over rows
+// rows[0 .. n-1] of X (device int32, strictly increasing; nullptr: rows 0 .. n-1); n <= 1024.
+hipError_t launch_meamed(const float* X, int64_t d, int64_t ldx, int ws, const int32_t* rows,
+                         int64_t n, int64_t keep, float* out, hipStream_t s);
+// The m rows of smallest score (ties to the lower index) -> flag [K], their indices
+// increasing -> list [m], their fp64 mean in that order -> out.
+hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, const float* X,
+                                  int64_t d, int64_t ldx, int ws, int32_t* flag, int32_t* list,
+                                  float* out, hipStream_t s);
+// Bulyan's theta selection rounds on D [K][K] (upper triangle): order [theta] in selection
+// order, list [theta] the same rows increasing; score [K], ord [K][K] (each row's columns by
+// stable rank) and alive [K] are scratch.
+hipError_t launch_bulyan_select(const double* D, int64_t K, int64_t f, int64_t theta,
+                                double* score, int32_t* ord, int32_t* alive, int32_t* order,
+                                int32_t* list, hipStream_t s);
 // Krum through the Gram (round 5): bounds + candidates from G [KP][KP] (lb, ub [K]; cand
 // [2 + maxc] int64: count, -1 (a bound not finite) or -2 (more than maxc), the indices, then
 // the row of the smallest upper bound), the candidates' exact rows (at most

@@ -305,6 +305,56 @@ enum gm_krum_reason {
 };
 int gm_krum_last_info(gm_ctx* ctx, int64_t* info);
 
+/* Three more robust aggregators on the same machinery (fp32 only; one entry each, `layout`
+ * GM_LAYOUT_ROWS: X as [K][ldx], ldx >= d, any alignment; GM_LAYOUT_PANELS: X as
+ * [ceil(d/W)][K][W], W = gm_panel_width(K), ldx = panel stride >= K*W).  X is never written;
+ * results are bit-identical for both layouts and every alignment.
+ *
+ * gm_meamed_f32: mean-around-median (Xie, Koyejo & Gupta 2018).  Per column, over the rows
+ * used (rows[0 .. n_rows-1], or all K when rows is NULL, then n_rows == K):
+ *   values are read as x + 0.0f (-0 becomes +0); med = their lower median (rank
+ *   (n_rows - 1) / 2, gm_median_f32's); dev_k = |x_k - med| as one fp32 subtraction; the
+ *   `keep` smallest dev are kept, ties at the threshold to the lower row index, a NaN dev
+ *   (inf - inf) ranking after +inf; out = the fp64 sum of the kept values in a fixed order,
+ *   divided by keep, rounded to fp32 once.  A NaN among the rows used gives NaN; infinities
+ *   follow IEEE through the subtraction and the sum.
+ *   rows   device int32[n_rows], strictly increasing indices into [0, K), or NULL.  It is NOT
+ *          validated: an entry outside [0, K) reads out of bounds.
+ * One stream-ordered kernel, one read of the rows used, no workspace, no host synchronisation.
+ * K <= 1024.
+ *
+ * gm_multi_krum_f32: Multi-Krum (Blanchard et al. 2017).  score_i = gm_krum_f32's (the sum of
+ * the honest - 1 smallest squared distances of row i, itself included), always on the exact
+ * distance path (GMAGG_KRUM is ignored); the m rows of smallest score are selected, ties to
+ * the lower row index; out = per column the fp64 sum of the selected rows in increasing row
+ * index, divided by m, rounded once.  m == 1 is gm_krum_f32's exact-path row, bit for bit.
+ * K <= 4096, 2 <= honest <= K + 1, 1 <= m <= K.
+ *   selected   host int32[m], the selected rows increasing, or NULL.  Non-NULL blocks until
+ *              the stream has run the call, like gm_krum_f32's index.
+ *
+ * gm_bulyan_f32: Bulyan (El Mhamdi, Guerraoui & Rouault 2018) with f = K - honest, K >= 4f + 3,
+ * theta = K - 2f, beta = theta - 2f.  Stage 1, theta rounds on the set S of remaining rows
+ * (all rows at first): the score of a row of S is the sum of its max(1, |S| - f - 1) smallest
+ * squared distances to rows of S, itself included; the row of smallest score (ties to the
+ * lower index) is selected and leaves S.  The distances are computed once (the exact path).
+ * Stage 2: gm_meamed_f32 with keep = beta over the selected rows in increasing row index
+ * (f == 0: the column mean).  K <= 1024.
+ *   selected   host int32[theta], the selected rows in selection order, or NULL (blocks as
+ *              above).
+ *
+ * GM_ERR_INVALID (nothing written): a NULL ctx, X or out, K < 1, d < 0, an unknown layout, ldx
+ * too small for its layout, keep / n_rows / m / honest out of range, K < 4f + 3.
+ * GM_ERR_UNSUPPORTED (with a message): K above the limit, panel input whose K has no panel
+ * width.  d == 0 returns GM_OK.  Multi-Krum and Bulyan use the context's workspace
+ * (stream-ordered with the other calls on it). */
+int gm_meamed_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                  const int32_t* rows, int64_t n_rows, int64_t keep, float* out, void* stream);
+int gm_multi_krum_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx,
+                      int32_t layout, int64_t honest, int64_t m, float* out, int32_t* selected,
+                      void* stream);
+int gm_bulyan_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                  int64_t honest, float* out, int32_t* selected, void* stream);
+
 /* getVarience(w_local, honestSize) (MNIST_Air_weight.py:127-129): the mean over the
  * first `honest` rows of ||x_k - mean||^2, written as ONE fp32 value to the device
  * pointer `out`; one streaming pass over the honest rows (fp64 sums). */
