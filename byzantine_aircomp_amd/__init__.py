@@ -10,6 +10,7 @@ reference's training loop.
 """
 from .aggregators import (GMResult, Krum, OMA, bucketed, bucketing, bulyan, cclip,  # noqa: F401
                           context, gm, gm2, meamed, mean, median, multi_krum, trimmed_mean)
+from .attacks import alie, ipm, minmax, minsum, z_max  # noqa: F401
 from .panels import ClientPanels, panel_width  # noqa: F401
 
 __version__ = "0.1.0"

@@ -131,6 +131,12 @@ SIGNATURES = [
                                       C.c_int32, _P]),
     ("gm_bucket_means_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _I64,
                                        C.c_int32, _P]),
+    ("gm_attack_affine_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, C.c_double,
+                                       C.c_double, _P]),
+    ("gm_attack_affine_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, C.c_double,
+                                        C.c_double, _P]),
+    ("gm_attack_minmax_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, C.c_int32,
+                                       C.c_int32, C.POINTER(C.c_double), _P]),
     ("gm_oma_apply_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     ("gm_client_chain_f32", C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64,
                                       C.c_int32, C.c_float, C.c_float, _P, _P, _P, _I64,

@@ -1,5 +1,6 @@
 // C ABI of libgmagg.so (include/gmagg.h): contexts, the coordinate-wise aggregators, Krum's
-// host side, MeaMed / Multi-Krum / Bulyan, OMA, the synthetic fills, the panel pack, s-bucketing and the client chain.  The Weiszfeld
+// host side, MeaMed / Multi-Krum / Bulyan, OMA, the synthetic fills, the panel pack, s-bucketing,
+// the omniscient attacks and the client chain.  The Weiszfeld
 // entry points are in host_weiszfeld.hip and host_batched.hip; what the three share is in
 // host_ctx.h.
 #include <cstring>
@@ -625,6 +626,86 @@ int gm_bucket_means_bf16(gm_ctx* c, const uint16_t* X, int64_t K, int64_t d, int
                          int32_t layout_out, void* stream) {
   return bucket_means("gm_bucket_means_bf16", c, X, true, K, d, ldx, layout_in, perm, s, Y, ldy,
                       layout_out, stream);
+}
+
+// ---- the omniscient attacks (attack.hip) ------------------------------------------------------
+
+// The common refusals of the attack entry points, then the panel shift (0 for rows).
+static int attack_shift(const char* fn, gm_ctx* c, const void* X, bool bf16, int64_t K, int64_t d,
+                        int64_t ldx, int32_t layout, int64_t byz, int* ws) {
+  if (!c || !X || K < 1 || d < 0 || !known_layout(layout) || byz < 1 || K - byz < 2)
+    return fail(GM_ERR_INVALID, "%s: bad args (a NULL ctx or X, K < 1, d < 0, an unknown layout, "
+                "byz < 1 or fewer than 2 honest rows)", fn);
+  if (!bf16 || layout == GM_LAYOUT_ROWS) return robust_shift(fn, K, d, ldx, layout, ws);
+  const int64_t W = gm_panel_width_bf16(K);
+  if (W == 0)
+    return fail(GM_ERR_UNSUPPORTED, "%s: no bf16 panel layout for K = %lld rows (pass them "
+                "row-major)", fn, (long long)K);
+  if (ldx < K * W)
+    return fail(GM_ERR_INVALID, "%s: panel stride %lld < K * W = %lld (W = gm_panel_width_bf16)",
+                fn, (long long)ldx, (long long)(K * W));
+  *ws = wshift_of(W);
+  return GM_OK;
+}
+
+static int attack_affine(const char* fn, gm_ctx* c, void* X, bool bf16, int64_t K, int64_t d,
+                         int64_t ldx, int32_t layout, int64_t byz, double a, double b,
+                         void* stream) {
+  int ws = 0;
+  const int rc = attack_shift(fn, c, X, bf16, K, d, ldx, layout, byz, &ws);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(launch_attack_affine(X, bf16, K, K - byz, d, ldx, ws, a, b,
+                              reinterpret_cast<hipStream_t>(stream)));
+  return GM_OK;
+}
+
+int gm_attack_affine_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                         int64_t byz, double a, double b, void* stream) {
+  return attack_affine("gm_attack_affine_f32", c, X, false, K, d, ldx, layout, byz, a, b, stream);
+}
+
+int gm_attack_affine_bf16(gm_ctx* c, uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                          int32_t layout, int64_t byz, double a, double b, void* stream) {
+  return attack_affine("gm_attack_affine_bf16", c, X, true, K, d, ldx, layout, byz, a, b, stream);
+}
+
+int gm_attack_minmax_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                         int64_t byz, int32_t rule, int32_t dev, double* gamma, void* stream) {
+  const char* fn = "gm_attack_minmax_f32";
+  int ws = 0;
+  int rc = attack_shift(fn, c, X, false, K, d, ldx, layout, byz, &ws);
+  if (rc) return rc;
+  if (rule < 0 || rule > 1 || dev < 0 || dev > 2)
+    return fail(GM_ERR_INVALID, "%s: rule %d (0 max, 1 sum) or dev %d (0 std, 1 unit, 2 sign)", fn,
+                rule, dev);
+  if (K > 4096) return fail(GM_ERR_UNSUPPORTED, "%s: K <= 4096 (got %lld)", fn, (long long)K);
+  if (d == 0) {
+    if (gamma) *gamma = 0.0;
+    return GM_OK;
+  }
+  const int64_t H = K - byz;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  // Krum's workspace on H rows (D in the G area, the slices' partials in the float slab), the
+  // iterate area as mu [d] and p [d] fp64, the slab as the row terms' slices
+  const int nb = attack_term_blocks(d);
+  const size_t part_doubles = (size_t)krum_slices(H, d) * (size_t)(H * H);
+  Workspace w;
+  rc = ensure_ws(c, H, 4 * d, nb, &w, 2 * part_doubles, (int)H);
+  if (rc) return rc;
+  double* mu = reinterpret_cast<double*>(w.g[0]);
+  // the panel shift and stride are K's: a row's address does not depend on the row count
+  HIPCHK(launch_krum_dist(X, H, d, ldx, ws, w.G, reinterpret_cast<double*>(w.gslab), s));
+  HIPCHK(launch_attack_minmax(X, K, H, d, ldx, ws, rule, dev, w.G, mu, mu + d, w.slab, nb, w.sums,
+                              w.alpha, w.r, s));
+  if (gamma) {
+    HIPCHK(hipMemcpyAsync(gamma, w.r + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  return GM_OK;
 }
 
 int gm_client_chain_f32(gm_ctx* c, const float* data, int64_t ldd, const int64_t* labels,

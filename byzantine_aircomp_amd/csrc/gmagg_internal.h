@@ -370,6 +370,22 @@ hipError_t launch_rows_to_panels_bf16(const void* X, bool src_f32, int64_t K, in
 hipError_t launch_bucket_means(const void* X, bool bf16, int64_t K, int64_t d, int64_t ldx,
                                int64_t Wi, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
                                int64_t Wo, hipStream_t stream);
+// The omniscient attacks (attack.hip), in place: rows H .. K-1 of X are overwritten from the
+// statistics of rows 0 .. H-1; ws = log2 of the panel width (0: rows), ldx the row or panel
+// stride.  Any alignment (4-column vector items where the base and stride allow).
+// Affine: every Byzantine row becomes a mu + b sigma (b == 0: a mu), rounded once to fp32 or
+// bf16 (X holds bf16 bit patterns).
+hipError_t launch_attack_affine(void* X, bool bf16, int64_t K, int64_t H, int64_t d, int64_t ldx,
+                                int ws, double a, double b, hipStream_t stream);
+// Min-max (rule 0) / min-sum (rule 1) with deviation dev (0 std, 1 unit, 2 sign), fp32: D [H][H]
+// the honest rows' squared distances (launch_krum_dist on H rows); workspace mu [d], p [d],
+// slab [nb][2H + 1] with nb = attack_term_blocks(d), sums [2H + 1], rb [H], gam [2] (written:
+// gamma for the kernels' p, then the definition's gamma).
+int attack_term_blocks(int64_t d);
+hipError_t launch_attack_minmax(float* X, int64_t K, int64_t H, int64_t d, int64_t ldx, int ws,
+                                int rule, int dev, const double* D, double* mu, double* p,
+                                double* slab, int nb, double* sums, double* rb, double* gam,
+                                hipStream_t stream);
 hipError_t launch_oma_philox(float* X, int64_t K, int64_t d, int64_t ldx, int64_t d_total,
                              int64_t col_off, float sd, uint64_t seed, hipStream_t s,
                              int wshift = 0, int64_t problems = 1, int64_t pstride = 0);

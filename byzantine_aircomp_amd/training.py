@@ -42,7 +42,8 @@ import torch
 import torch.nn as nn
 
 __all__ = ["ClientUpdates", "SGD", "run", "modelFactory", "MLP", "setup_seed",
-           "calculateAccuracy", "getVarience", "classflip", "dataflip", "weightflip"]
+           "calculateAccuracy", "getVarience", "classflip", "dataflip", "weightflip",
+           "ATTACK_NAMES", "attack_by_name"]
 
 
 # ---- small pieces with the reference's semantics -------------------------------
@@ -130,6 +131,26 @@ def weightflip(messages, byzantinesize):
         return
     honest_sum = messages[:-byzantinesize].sum(dim=0)
     messages[-byzantinesize:].mul_(-1).add_(honest_sum / byzantinesize, alpha=-2)
+
+
+# run(..., attack="name"): the reference's three, and the omniscient attacks of attacks.py
+ATTACK_NAMES = ("classflip", "dataflip", "weightflip", "alie", "ipm", "minmax", "minsum")
+
+
+def attack_by_name(name):
+    """The attack function ``run`` uses for a name in ATTACK_NAMES (KeyError otherwise).
+
+    alie, ipm, minmax and minsum (attacks.py) rewrite the Byzantine rows of the client matrix
+    from the honest rows' statistics, after the clients' local steps.  The fused client
+    kernel maps a name it does not know to honest local steps (``_ClientChain.ATTACK``), as
+    the torch loop does: under these four the Byzantine clients train honestly and their
+    rows are then overwritten."""
+    if name in ("classflip", "dataflip", "weightflip"):
+        return {"classflip": classflip, "dataflip": dataflip, "weightflip": weightflip}[name]
+    if name not in ATTACK_NAMES:
+        raise KeyError(name)
+    from . import attacks
+    return getattr(attacks, name)
 
 
 def _oma_host(message, noise_var):
@@ -299,6 +320,9 @@ def SGD(model, gamma, aggregate, weight_decay, noise_var=None, honestSize=0,  # 
     TensorDataset, the K client steps of a federated step run as ONE HIP kernel
     (gm_client_chain_f32) instead of K host-driven forward/backward passes; True
     requires it, False keeps the per-client torch loop.
+    attack: classflip / dataflip act inside the clients' steps; any other attack (weightflip,
+    attacks.alie / ipm / minmax / minsum) is called on the client matrix after the clients'
+    honest local steps and overwrites the Byzantine rows.
     EMNIST_Air_weight.py's variant: num_classes=62 (its MLP(784, 62) and 61 - y
     relabel, E:101, E:321) and eval_train=False (train loss / accuracy recorded as
     0, 0, E:273-274, E:364-365)."""
@@ -402,7 +426,7 @@ def run(optimizer, aggregate, attack, config, noise_var=None, dataSetConfig=None
     if attack is None:
         cfg["byzantineSize"] = 0
     elif isinstance(attack, str):
-        attack = {"classflip": classflip, "dataflip": dataflip, "weightflip": weightflip}[attack]
+        attack = attack_by_name(attack)
     cfg.update(aggregate=aggregate, attack=attack, noise_var=noise_var)
     model = modelFactory(SEED=cfg["SEED"], num_classes=num_classes)
     if device is not None and device != torch.device("cpu"):

@@ -434,6 +434,55 @@ int gm_bucket_means_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, i
                          int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
                          int32_t layout_out, void* stream);
 
+/* Omniscient model-poisoning attacks, in place on the client matrix: rows 0 .. H-1 (H = K - byz
+ * >= 2) are the honest clients, rows H .. K-1 the Byzantine ones (the reference's
+ * messages[-byzantinesize:]), which are overwritten with ONE malicious row computed from the
+ * honest rows' per-column statistics, in fp64 (bf16 inputs widened exactly):
+ *     mu_j    = (sum_{k<H} x_kj) / H, summed in increasing k
+ *     sigma_j = sqrt(sum_{k<H} (x_kj - mu_j)^2 / (H - 1))     (the unbiased estimate)
+ * sigma comes from sums shifted by the column's first row, clamped at 0: a column whose honest
+ * values are all equal has sigma_j == 0 and mu_j == that value exactly.
+ *
+ * gm_attack_affine_f32 / _bf16: every Byzantine row becomes y_j = a mu_j + b sigma_j, rounded
+ * once to the storage type (bf16: to nearest even).  a = 1, b = -z is "A Little Is Enough"
+ * (Baruch, Baruch & Goldberg 2019), a = -epsilon, b = 0 inner-product manipulation (Xie, Koyejo
+ * & Gupta 2019).  b == 0 forms no sigma term (a column holding +inf gives a * inf, not NaN);
+ * a NaN among a column's honest values gives NaN; infinities follow IEEE.
+ *   X      fp32, or bfloat16 bit patterns; layout GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any
+ *          alignment) or GM_LAYOUT_PANELS ([ceil(d/W)][K][W], W = gm_panel_width(K) resp.
+ *          gm_panel_width_bf16(K), ldx = panel stride >= K*W).  Only columns < d of rows >= H
+ *          are written: the honest rows and the panels' padding columns keep their bits.
+ * One stream-ordered kernel that reads H*d elements once and writes byz*d: no workspace, no host
+ * synchronisation.  The result is bit-identical for every layout and alignment of one type,
+ * and column-local: on a d-sharded matrix every rank attacks its own columns with the same a, b.
+ *
+ * gm_attack_minmax_f32 (fp32 only): the min-max (rule 0) and min-sum (rule 1) attacks of
+ * Shejwalkar & Houmansadr 2021.  Every Byzantine row becomes m = mu - gamma p, rounded once, with
+ * the deviation p = sigma (dev 0), mu / ||mu|| (dev 1) or sign(mu) (dev 2) and the largest gamma
+ * that meets
+ *     rule 0   max_i ||m - x_i||^2 <= max_ij ||x_i - x_j||^2 =: D*
+ *              gamma = min_i (b_i + sqrt(b_i^2 + c (D* - a_i))) / c
+ *     rule 1   sum_i ||m - x_i||^2 <= max_i sum_j ||x_i - x_j||^2 =: S*
+ *              gamma = sqrt((S* - sum_i a_i) / (H c))
+ * over the honest rows, where a_i = ||mu - x_i||^2, b_i = p . (mu - x_i), c = ||p||^2 (fp64 sums
+ * in a fixed order); c == 0 gives gamma = 0, m = mu.  The pairwise distances are gm_krum_f32's
+ * exact path on the H honest rows (fp32 squares summed per 32-column stage, fp64 across stages),
+ * hence K <= 4096.  Not column-local.
+ *   gamma   host double, or NULL.  Non-NULL receives gamma and blocks until the stream has run
+ *           the call; the row is written from the device-side value either way.
+ * Uses the context's workspace (stream-ordered with the other calls on it).
+ *
+ * GM_ERR_INVALID (nothing written): a NULL ctx or X, K < 1, d < 0, byz < 1, K - byz < 2, an
+ * unknown layout, rule or dev, ldx too small for its layout.  GM_ERR_UNSUPPORTED (with a
+ * message): panel input whose K has no panel width of its type, K > 4096 (min-max / min-sum).
+ * d == 0 returns GM_OK. */
+int gm_attack_affine_f32 (gm_ctx* ctx, float*    X, int64_t K, int64_t d, int64_t ldx,
+                          int32_t layout, int64_t byz, double a, double b, void* stream);
+int gm_attack_affine_bf16(gm_ctx* ctx, uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                          int32_t layout, int64_t byz, double a, double b, void* stream);
+int gm_attack_minmax_f32 (gm_ctx* ctx, float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+                          int64_t byz, int32_t rule, int32_t dev, double* gamma, void* stream);
+
 /* The K clients' local SGD steps of one federated step (the loop body M:291-343:
  * forward, CrossEntropyLoss (mean), backward, p -= gamma * (grad + weight_decay * p),
  * the client's parameters copied out as its row), as one stream-ordered kernel, for the
