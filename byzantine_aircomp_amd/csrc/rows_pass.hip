@@ -1,5 +1,7 @@
 // The fused Weiszfeld pass on the reference's own row-major [K, ldx] stack at 512 < K <= 1024
-// (round 6): the drop-in layout's STEP pass for gm2 (M:174-181, stream_pass.hip's algorithm).
+// (round 6): the drop-in layout's STEP pass for gm2 (M:174-181, stream_pass.hip's algorithm)
+// and for AirComp gm without channel noise (noise_var = None), whose STEP pass is the same
+// arithmetic: g' = sum_k c_k x_k with the K-space step's coefficients and no column term.
 //
 // Why a second kernel for the same arithmetic.  On row-major X every 128-byte row segment of
 // a chunk lies in its own 2 MB page (rows are 4 * ldx bytes apart), so the per-CU address
@@ -10,7 +12,7 @@
 // per CU instead of 16 — two 1024-thread blocks, each thread holding 8 rows x 4 columns (32
 // floats instead of stream_pass's 64), which the generic template cannot fit in the 64
 // VGPRs that occupancy allows (it spills 40-83).  This kernel is that tile with nothing
-// else: gm2 only (no column noise, no OMA), rows through buffer resources whose range check
+// else: no column term (gm2 and noiseless gm; no column noise, no OMA), rows through buffer resources whose range check
 // zeroes rows >= K (no per-row masks), the row weights and the finisher threads' movement /
 // norm partials in LDS, every cross-lane sum on DPP / permlane moves (no index registers):
 // 1-6 VGPRs spilled.  Measured at C3 on rows (profiles/r6s1_rows_lean32w_dpp_ab.jsonl, four
@@ -195,13 +197,17 @@ __global__ void __launch_bounds__(kRW * 64, 8) rows_pass(PassArgs a) {
   }
 }
 
-// GMAGG_ROWS_LEAN (read per call): 1 (default) this kernel for the row-major gm2 STEP passes,
-// 2 the INIT pass too, 0 the generic stream_pass tile (A/B, tests)
+// GMAGG_ROWS_LEAN (read per call): 1 (default) this kernel for the row-major STEP passes of gm2
+// and noiseless gm, 2 gm2's INIT pass too, 0 the generic stream_pass tile (A/B, tests)
 static bool rows_lean_on() {
   const char* e = getenv("GMAGG_ROWS_LEAN");
   return e ? atoi(e) != 0 : true;
 }
 
+// Eligible: a STEP pass without a column term (PassArgs.noise == 0: gm2, and AirComp gm with
+// noise_var = None; AirComp gm with channel noise and centered clipping stay on the generic
+// tile) of one row-major problem with float4 rows at 512 < K <= 1024.  Both are pinned against
+// fp64 and against GMAGG_ROWS_LEAN=0 by tests/test_gpu_stream_tiles.py.
 bool rows_pass_eligible(const PassArgs& a, int mode) {
   // STEP only: the INIT pass stays on the generic tile so that gm2 with the fused OMA
   // pre-noise (INIT mode 4, generic) and OMA followed by gm2 (INIT mode 1) keep computing the

@@ -9,7 +9,10 @@ segments, 4*d bytes apart.  ``ClientPanels`` stores the same K x d values as
 each chunk is ONE contiguous block of HBM.  It is the device-resident buffer a
 training loop writes client rows into (``store``), and ``gm2`` / ``gm`` accept it
 wherever they accept a ``[K, d]`` tensor; results are bit-identical to the
-row-major call (same chunks, same reduction order).
+row-major call where both layouts run the same tile (same chunks, same reduction
+order): every K outside 32 < K <= 64 and 128 < K <= 256 with d % 4 == 0, except
+gm2 and noiseless AirComp gm at 512 < K <= 1024, whose row-major STEP pass runs
+the 32-wave rows kernel; equal to rounding otherwise.
 
 ``ClientPanels(..., dtype=torch.bfloat16)`` stores the values as bf16 in the layout of
 ``gm_weiszfeld_bf16`` (W = ``gm_panel_width_bf16(K)``): half the bytes per streaming pass.
