@@ -314,7 +314,7 @@ __global__ void __launch_bounds__(NW * 64) weiszfeld_resident(ResArgs a) {
   const int64_t ch0 = (int64_t)bid * CPB;          // first chunk of this block
   const int64_t gj = ch0 * J + tid;                // finisher column (tid < JB)
   const bool fin = tid < JB && gj < d;
-  gu64* gran = (gu64*)a.gran;                      // [2][nb][2 NV]
+  gu64* gran = (gu64*)a.gran;                      // [2][nb][NV]: one granule per value
   gu32* tmo = (gu32*)a.bar + 2;
   // every block of the grid co-resident before anything is read (device_util.h)
   if (!grid_checkin(a.checkin, slot, a.need, a.bar + 2, a.bar + 3, kCheckinTicks, &s_ok, &s_same,

@@ -201,7 +201,8 @@ __device__ __forceinline__ void rb_all_rows(F f, float* srow, int lane) {
 // LDS rows' loads, 256 the register rows' loads
 template <int KR, int KV, int MODE, int DBG = 0, int XG = 0>
 __global__ void __launch_bounds__(512) weiszfeld_resident_batched(ResBArgs a) {
-  // KR rows per column (K rounded up to 4): rows [0, KV) live in the thread's VGPRs, rows
+  // KR rows per column (K rounded up to the row tile: 16, 32, 50 or 52; rows past K load as
+  // zeros and get coefficient 0): rows [0, KV) live in the thread's VGPRs, rows
   // [KV, KR) in LDS (s_x, the thread's own 16 bytes per row).  MODE: gm_mode, a template
   // parameter so that the gm2 kernel carries none of the AirComp code's registers.
   static_assert(KR % 2 == 0 && KV % 4 == 0 && KV <= KR && KR <= 64, "rows per thread");
@@ -778,8 +779,9 @@ __global__ void __launch_bounds__(512) weiszfeld_resident_batched(ResBArgs a) {
 
 // ---------------------------------------------------------------------------
 
-// (rows, rows in VGPRs): K <= 32 wholly in registers; K <= 52 with rows 36..51 in LDS
-// (a 52-row register tile does not fit 256 VGPRs beside the kernel's own ~90)
+// (rows, rows in VGPRs): K <= 32 wholly in registers; K <= 50 with rows 32..49 in LDS and
+// K = 51, 52 with rows 36..51 in LDS (a 52-row register tile does not fit 256 VGPRs beside
+// the kernel's own ~90)
 static const void* rb_kernel(int kr, int mode, int xg = 0) {
 #ifdef GMK_RB_DBG_VARIANTS
   static const int dbg = getenv("GMAGG_RB_DBG") ? atoi(getenv("GMAGG_RB_DBG")) : 0;
