@@ -115,6 +115,8 @@ SIGNATURES = [
     ("gm_meamed_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _I64, _P, _P]),
     ("gm_multi_krum_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _I64, _P, _P, _P]),
     ("gm_bulyan_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _P, _P, _P]),
+    ("gm_nnm_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _P, _I64, C.c_int32, _P,
+                             _P]),
     ("gm_oma_philox_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_double, C.c_uint64, _P]),
     ("gm_honest_variance_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("gm_honest_variance_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P]),

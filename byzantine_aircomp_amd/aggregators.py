@@ -48,6 +48,9 @@ selection, then a mean around the median) and ``meamed(wList, options)`` (Xie, K
 2018: per coordinate the mean of the ``honestSize`` values nearest to the median) take fp32
 rows or panels and ``honestSize`` like ``Krum``; they work under ``bucketed`` and as a
 training loop's ``aggregate``.
+``nnm(wList, f)`` is nearest-neighbor mixing (Allouah et al., AISTATS 2023): every row replaced
+by the mean of its K - f nearest rows, fp32 rows or panels in and out; ``mixed(aggregate)``
+wraps any aggregator above with it.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -67,7 +70,7 @@ from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
-           "multi_krum", "bulyan", "meamed"]
+           "multi_krum", "bulyan", "meamed", "nnm", "mixed"]
 
 
 @dataclass
@@ -793,6 +796,101 @@ def bucketed(aggregate, s, generator=None, layout="panels"):
 
     agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_b{s}"
     agg.__doc__ = f"{aggregate.__name__} on the bucket means of s = {s} bucketing"
+    return agg
+
+
+def _nnm_f(f, K: int, who: str) -> int:
+    """f as an int in [0, K - 1]; ValueError otherwise (a float, a bool, out of range)."""
+    try:
+        if isinstance(f, bool):
+            raise TypeError
+        n = operator.index(f)
+    except TypeError:
+        raise ValueError(f"{who}: f must be an integer in [0, {K - 1}] (got {f!r})") from None
+    if not 0 <= n <= K - 1:
+        raise ValueError(f"{who}: f = {n} not in [0, {K - 1}]")
+    return n
+
+
+def _has_panels(K: int) -> bool:
+    return int(_lib.load().gm_panel_width(int(K))) > 0
+
+
+def nnm(wList, f, layout=None, neighbors=False):
+    """Nearest-neighbor mixing (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot & Stephan, "Fixing
+    by Mixing: A Recipe for Optimal Byzantine ML under Heterogeneity", AISTATS 2023, Algorithm
+    1), the pre-step under which the robust rules reach the optimal heterogeneity bound: every
+    client update is replaced by the mean of its K - f nearest updates, itself included.
+    Deterministic; all K rows are kept, so ``honestSize`` is unchanged.  Three HIP steps
+    (gm_nnm_f32): the exact pair distances multi_krum scores, each row's K - f nearest by
+    (distance, index), and the mixing pass (nnm.hip), whose every element is the fp64 sum of its
+    K - f terms in increasing row index, divided, rounded once: bit-identical whatever the
+    input or output layout.  A row outside a neighbourhood contributes nothing to it, whatever
+    it holds (huge, inf, NaN).
+
+    wList: an fp32 [K, d] tensor (any stride or alignment; a CPU tensor is staged to the GPU and
+    the row-major result copied back) or fp32 ClientPanels, K <= 4096; never written.  f: an
+    integer in [0, K - 1] (``f == 0``: every row becomes the column mean).  Returns the mixed
+    rows as fp32: with ``layout=None`` a [K, d] tensor for a tensor and ``ClientPanels(K, d)``
+    for ClientPanels; ``"rows"`` / ``"panels"`` force one.  ``neighbors=True`` returns
+    ``(Y, N)`` with N the int32 [K, K - f] neighbour lists (increasing within a row) on the GPU.
+    bf16 inputs, d-sharded contexts and K > 4096 are refused."""
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"nnm: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    K, d = _robust_shape(wList, "nnm")
+    f = _nnm_f(f, K, "nnm")
+    if K > 4096:
+        raise ValueError(f"nnm: K <= 4096 (got {K})")
+    panels_out = layout == "panels" or (layout is None and isinstance(wList, ClientPanels))
+    if panels_out and not _has_panels(K):
+        raise ValueError(f"nnm: no panel layout for K = {K} rows (take them row-major)")
+    X, ldx, lin, K, d = _robust_operand(wList, "nnm")
+    m = K - f
+    if panels_out:
+        out = ClientPanels(K, d, device=X.device, zero=False)    # every column < d is written
+        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        out = Y = torch.empty(K, d, dtype=torch.float32, device=X.device)
+        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    N = torch.empty(K, m, dtype=torch.int32, device=X.device) if neighbors else None
+    if d > 0:
+        context(X.device).call("gm_nnm_f32", X.data_ptr(), K, d, ldx, lin, f, Y.data_ptr(), ldy,
+                               lout, N.data_ptr() if neighbors else None, _stream_ptr(X.device))
+    elif neighbors:                      # every distance is 0: the m rows of lowest index
+        N.copy_(torch.arange(m, dtype=torch.int32, device=X.device).expand(K, m))
+    if out is Y and wList.device != Y.device:
+        out = Y.to(wList.device)
+    return (out, N) if neighbors else out
+
+
+def mixed(aggregate, f=None, layout="panels"):
+    """An ``aggregate(wList, options)`` callable that mixes wList (``nnm``) and calls `aggregate`
+    on the mixed rows, handed over in `layout` ("panels", the layout the streaming pass reads
+    fastest — rows where K has no panel width — "rows", or None for wList's own).  Named
+    ``f"{aggregate.__name__}_nnm"``; works with every aggregator ``bucketed`` lists, and as
+    ``training.run(..., aggregate=mixed(gm2))``.
+
+    f: the number of Byzantine clients to mix against; None takes ``K - options['honestSize']``
+    per call (ValueError without it).  Options pass through unchanged (NNM keeps all K rows, so
+    ``honestSize`` stands); the caller's dict is not modified.  The result lives on
+    wList.device, as the aggregators' own."""
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"mixed: layout must be None, 'rows' or 'panels' (got {layout!r})")
+
+    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+        K = int(wList.shape[0])
+        if f is None:
+            f_ = K - _honest_size(options, agg.__name__)
+        else:
+            f_ = f
+        lay = "rows" if layout == "panels" and K >= 1 and not _has_panels(K) else layout
+        out = aggregate(nnm(wList, f_, layout=lay), options)
+        if isinstance(out, torch.Tensor) and out.device != wList.device:
+            out = out.to(wList.device)        # (a CPU wList's mixed rows stayed on the GPU as panels)
+        return out
+
+    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_nnm"
+    agg.__doc__ = f"{aggregate.__name__} on the rows mixed by nearest-neighbor mixing"
     return agg
 
 

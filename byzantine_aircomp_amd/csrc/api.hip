@@ -1,5 +1,6 @@
 // C ABI of libgmagg.so (include/gmagg.h): contexts, the coordinate-wise aggregators, Krum's
-// host side, MeaMed / Multi-Krum / Bulyan, OMA, the synthetic fills, the panel pack, s-bucketing,
+// host side, MeaMed / Multi-Krum / Bulyan, nearest-neighbor mixing, OMA, the synthetic fills,
+// the panel pack, s-bucketing,
 // the omniscient attacks and the client chain.  The Weiszfeld
 // entry points are in host_weiszfeld.hip and host_batched.hip; what the three share is in
 // host_ctx.h.
@@ -486,6 +487,47 @@ int gm_bulyan_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, 
   HIPCHK(launch_bulyan_select(w.G, K, f, theta, w.alpha, ord, alive, picked, list, s));
   HIPCHK(launch_meamed(X, d, ldx, ws, list, theta, beta, out, s));
   return copy_selected(selected, picked, theta, s);
+}
+
+// GMAGG_NNM_STOP (read per call; tools/nnm_bench.py times the steps apart with it): 1 returns
+// after the distances, 2 after the neighbours; anything else runs the whole call.
+static int nnm_stop() { return env_int("GMAGG_NNM_STOP", 0); }
+
+int gm_nnm_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout_in,
+               int64_t f, float* Y, int64_t ldy, int32_t layout_out, int32_t* neighbors,
+               void* stream) {
+  if (!c || !X || !Y || K < 1 || d < 0 || f < 0 || f > K - 1 || !known_layout(layout_in) ||
+      !known_layout(layout_out))
+    return fail(GM_ERR_INVALID, "gm_nnm_f32: bad args (a NULL ctx, X or Y, K < 1, d < 0, f outside "
+                "[0, K - 1] or an unknown layout)");
+  if (K > 4096) return fail(GM_ERR_UNSUPPORTED, "gm_nnm_f32: K <= 4096 (got %lld)", (long long)K);
+  int ws = 0, wsy = 0;
+  int rc = robust_shift("gm_nnm_f32", K, d, ldx, layout_in, &ws);
+  if (rc) return rc;
+  rc = robust_shift("gm_nnm_f32", K, d, ldy, layout_out, &wsy);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  if (c->d_total > 0 || c->comm || c->ar_fn)
+    return fail(GM_ERR_UNSUPPORTED, "gm_nnm_f32: a d-sharded or collective context (the distances would need a "
+                "K x K all-reduce)");
+  const int64_t m = K - f;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  // Krum's workspace (D in the G area, the slices' partials in the float slab); the partials
+  // are dead once D is reduced, and the slab then holds the mask
+  const size_t part_doubles = (size_t)krum_slices(K, d) * (size_t)(K * K);
+  Workspace w;
+  rc = ensure_ws(c, K, 1, 1, &w, std::max(2 * part_doubles, (size_t)nnm_mask_words(K)), (int)K);
+  if (rc) return rc;
+  HIPCHK(launch_krum_dist(X, K, d, ldx, ws, w.G, reinterpret_cast<double*>(w.gslab), s));
+  const int stop = nnm_stop();
+  if (stop == 1) return GM_OK;
+  uint32_t* mask = reinterpret_cast<uint32_t*>(w.gslab);
+  HIPCHK(launch_nnm_neighbors(w.G, K, m, mask, neighbors, s));
+  if (stop == 2) return GM_OK;
+  HIPCHK(launch_nnm_mix(X, K, d, ldx, ws, mask, m, Y, ldy, wsy, s));
+  return GM_OK;
 }
 
 int gm_oma_philox_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, double noise_var,

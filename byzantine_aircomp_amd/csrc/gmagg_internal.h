@@ -370,6 +370,19 @@ hipError_t launch_rows_to_panels_bf16(const void* X, bool src_f32, int64_t K, in
 hipError_t launch_bucket_means(const void* X, bool bf16, int64_t K, int64_t d, int64_t ldx,
                                int64_t Wi, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
                                int64_t Wo, hipStream_t stream);
+// Nearest-neighbor mixing (nnm.hip).  From D [K][K] (launch_krum_dist) the membership of every
+// row's m nearest rows, itself included, in the order of score_before: mask
+// [nnm_mask_words(K)] = [K][2 ceil(K / 64)] words, bit j & 31 of word j >> 5 of row i set when
+// j is in N(i); list (nullable, device) [K][m] the same members increasing.  K <= 4096.
+int64_t nnm_mask_words(int64_t K);
+hipError_t launch_nnm_neighbors(const double* D, int64_t K, int64_t m, uint32_t* mask,
+                                int32_t* list, hipStream_t s);
+// Y[i] = the fp64 sum of the rows of N(i) in increasing row index, divided by m, rounded once.
+// X rows (ws = 0) or panels of width 2^ws, Y rows (wsy = 0, any ldy >= d) or panels of width
+// 2^wsy; any alignment; columns >= d of Y are not written.
+hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                          const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
+                          hipStream_t s);
 // The omniscient attacks (attack.hip), in place: rows H .. K-1 of X are overwritten from the
 // statistics of rows 0 .. H-1; ws = log2 of the panel width (0: rows), ldx the row or panel
 // stride.  Any alignment (4-column vector items where the base and stride allow).

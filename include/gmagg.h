@@ -434,6 +434,38 @@ int gm_bucket_means_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, i
                          int32_t layout_in, const int32_t* perm, int64_t s, float* Y, int64_t ldy,
                          int32_t layout_out, void* stream);
 
+/* Nearest-neighbor mixing, NNM (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot & Stephan, "Fixing
+ * by Mixing: A Recipe for Optimal Byzantine ML under Heterogeneity", AISTATS 2023, Algorithm 1),
+ * the pre-step of every aggregator above under heterogeneity: every row is replaced by the mean
+ * of its m = K - f nearest rows, itself included.  Y has K rows; X is fp32 [K, d], never written;
+ * 0 <= f <= K - 1.
+ *   1. Distances.  D[i][j] is the exact path's squared distance (gm_multi_krum_f32's: fp32
+ *      differences, fp32 squares summed per 32-column stage, fp64 across stages), with
+ *      D[i][i] = 0 whatever the row holds.
+ *   2. Neighbours.  N(i) is the m rows j first in the order of (D[i][j], j): smaller distance
+ *      first, NaN last, ties to the lower index.  i is in N(i) unless m or more rows of lower
+ *      index lie at distance exactly 0 (copies of row i: the mean is the same whichever copy is
+ *      taken).  A NaN or +-inf distance is ranked by the same rule.
+ *   3. Mixing.  Y[i][j] = (sum over k in N(i) of X[k][j]) / m: the fp64 sum of exactly those m
+ *      terms, divided in fp64, rounded to fp32 once.  A NaN term gives NaN, infinities follow
+ *      IEEE; a row outside N(i) contributes nothing, whatever it holds.
+ *   4. The terms are added in increasing k, so the result is a function of (K, d, N) only:
+ *      bit-identical for rows, panels and every alignment of X and Y.  (The complement form,
+ *      column sum minus the excluded rows, is not used: it cancels when the excluded rows are
+ *      the huge Byzantine ones.)
+ *   X          layout_in GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any alignment) or GM_LAYOUT_PANELS
+ *              ([ceil(d/W)][K][W], W = gm_panel_width(K), ldx = panel stride >= K*W).
+ *   Y          layout_out likewise with ldy (rows: any ldy >= d); columns >= d are not written.
+ *   neighbors  device int32 [K][K - f], each row's members increasing, or NULL.
+ * Stream-ordered on the context's workspace like gm_multi_krum_f32; no host synchronisation.
+ * GM_ERR_INVALID (nothing written): a NULL ctx, X or Y, K < 1, d < 0, f outside [0, K - 1], an
+ * unknown layout, ldx or ldy too small for its layout.  GM_ERR_UNSUPPORTED (with a message):
+ * K > 4096, a panel layout whose K has no panel width, a d-sharded or collective context (the
+ * distances would need a K x K all-reduce).  d == 0 returns GM_OK before any device call. */
+int gm_nnm_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout_in,
+               int64_t f, float* Y, int64_t ldy, int32_t layout_out, int32_t* neighbors,
+               void* stream);
+
 /* Omniscient model-poisoning attacks, in place on the client matrix: rows 0 .. H-1 (H = K - byz
  * >= 2) are the honest clients, rows H .. K-1 the Byzantine ones (the reference's
  * messages[-byzantinesize:]), which are overwritten with ONE malicious row computed from the
