@@ -51,6 +51,12 @@ training loop's ``aggregate``.
 ``nnm(wList, f)`` is nearest-neighbor mixing (Allouah et al., AISTATS 2023): every row replaced
 by the mean of its K - f nearest rows, fp32 rows or panels in and out; ``mixed(aggregate)``
 wraps any aggregator above with it.
+``dnc(wList, options)`` is Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021): spectral
+filtering on ``dnc_dims`` sampled columns, in fp64: the rows whose centred projections on the
+sample's top singular vector are largest are dropped (``int(dnc_c * f)`` per round, ``dnc_iters``
+rounds) and the rest averaged; fp32 rows or panels and ``honestSize`` like ``Krum``;
+``dnc.with_options(...)`` fixes its options; it works under ``bucketed`` and ``mixed`` and as a
+training loop's ``aggregate``.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -70,7 +76,7 @@ from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
-           "multi_krum", "bulyan", "meamed", "nnm", "mixed"]
+           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc"]
 
 
 @dataclass
@@ -892,6 +898,148 @@ def mixed(aggregate, f=None, layout="panels"):
     agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_nnm"
     agg.__doc__ = f"{aggregate.__name__} on the rows mixed by nearest-neighbor mixing"
     return agg
+
+
+_DNC_KEYS = ("dnc_iters", "dnc_dims", "dnc_c", "dnc_columns", "generator", "power_iters",
+             "power_tol")
+_DNC_MAX_ELEMS = 1 << 27          # gm_dnc_f32's cap on K * n
+
+
+def _dnc_scalars(options):
+    """(iters, b, c, power_iters, power_tol) from the options; ValueError on an invalid value."""
+    iters = int(options.get("dnc_iters", 1))
+    if iters < 1:
+        raise ValueError(f"dnc: dnc_iters must be >= 1 (got {options.get('dnc_iters')!r})")
+    b = int(options.get("dnc_dims", 10000))
+    if b < 1:
+        raise ValueError(f"dnc: dnc_dims must be >= 1 (got {options.get('dnc_dims')!r})")
+    c = float(options.get("dnc_c", 1.0))
+    if not 0 <= c < math.inf:                         # (NaN fails too)
+        raise ValueError(f"dnc: dnc_c must be >= 0 (got {options.get('dnc_c')!r})")
+    pit = int(options.get("power_iters", 100))
+    if pit < 1:
+        raise ValueError(f"dnc: power_iters must be >= 1 (got {options.get('power_iters')!r})")
+    ptol = float(options.get("power_tol", 1e-10))
+    if not ptol >= 0:
+        raise ValueError(f"dnc: power_tol must be >= 0 (got {options.get('power_tol')!r})")
+    return iters, b, c, pit, ptol
+
+
+def _dnc_draw(d, b, iters, generator=None) -> torch.Tensor:
+    """The columns DnC samples, an int64 [iters, min(b, d)] CPU tensor, each row increasing.
+    b < d: per round ``torch.randperm(d, generator=generator)[:b]``, sorted, one draw per round
+    (from the global CPU generator when no generator is given).  b >= d: every round is
+    ``arange(d)`` and nothing is drawn.  A draw costs O(d) on the host per round, whatever b."""
+    d, b, iters = int(d), int(b), int(iters)
+    if d < 1 or b < 1 or iters < 1:
+        raise ValueError(f"dnc.columns: d, b and iters must be >= 1 (got {d}, {b}, {iters})")
+    if b >= d:
+        return torch.arange(d).repeat(iters, 1)
+    return torch.stack([torch.sort(torch.randperm(d, generator=generator)[:b]).values
+                        for _ in range(iters)])
+
+
+def _dnc_given_columns(cols, iters: int, d: int) -> torch.Tensor:
+    """options['dnc_columns'] as a CPU int64 [iters, n] tensor, checked on the host (the kernel
+    does not check: a bad index would read outside the matrix)."""
+    p = torch.as_tensor(cols).detach().cpu()
+    if p.dtype.is_floating_point or p.dtype == torch.bool or p.dtype.is_complex:
+        raise ValueError(f"dnc: dnc_columns must hold integers (got {p.dtype})")
+    if p.dim() == 1 and iters == 1:
+        p = p[None]
+    if p.dim() != 2 or p.shape[0] != iters or not 1 <= p.shape[1] <= d:
+        raise ValueError(f"dnc: dnc_columns must be [{iters}, n] with 1 <= n <= {d} "
+                         f"(got {tuple(p.shape)})")
+    p = p.to(torch.int64).contiguous()
+    if int(p.min()) < 0 or int(p.max()) >= d:
+        raise ValueError(f"dnc: dnc_columns outside [0, {d - 1}]")
+    if p.shape[1] > 1 and not bool((p[:, 1:] > p[:, :-1]).all()):
+        raise ValueError("dnc: every row of dnc_columns must be strictly increasing")
+    return p
+
+
+def dnc(wList, options):
+    """Divide-and-Conquer (Shejwalkar & Houmansadr, "Manipulating the Byzantine", NDSS 2021,
+    Algorithm 2), the spectral filter published with the min-max / min-sum attacks: ``dnc_iters``
+    (default 1) times, sample ``dnc_dims`` (b, default 10000; b >= d takes every column) columns,
+    centre the K x b sub-matrix, find its top right singular vector v by power iteration, score
+    every row by (c_k . v)^2 and keep the K - q rows of smallest score, q = int(dnc_c * f),
+    ``dnc_c`` default 1.0, f = K - honestSize; the result is the mean of the rows every round
+    kept.  All of it in fp64 on the GPU (gm_dnc_f32: the gather, the iteration and the scores in
+    dnc.hip, then multi_krum's selection and mean); include/gmagg.h has the definition, tie rules
+    and start vector.  Bit-identical for rows, panels and every alignment; q == 0 is ``mean``.
+
+    wList: an fp32 [K, d] tensor (any stride; a CPU tensor is staged and the result copied back)
+    or fp32 ClientPanels, 2 <= K <= 4096, K * b <= 2^27; never written.  bf16, fp64 (TypeError),
+    a missing ``honestSize``, q * dnc_iters >= K, dnc_c < 0, dnc_iters < 1 (ValueError) are
+    refused before a GPU is touched.  Other options: ``power_iters`` (100) and ``power_tol``
+    (1e-10), the iteration's cap and its stop on the unit iterate's movement; ``generator`` for
+    the column draw (``dnc.columns(d, b, iters, generator)``: ``torch.randperm(d)[:b]`` sorted,
+    per round, O(d) host work per round whatever b); ``dnc_columns``, an explicit integer
+    [dnc_iters, n] tensor, each row strictly increasing in [0, d), which replaces the draw and
+    its cost.  Every other key is ignored.
+
+    After a call ``dnc.last_columns`` holds the columns used (CPU int64 [dnc_iters, n]; n = 0 when
+    q == 0: nothing is drawn), ``dnc.last_selected`` the good rows, increasing,
+    ``dnc.last_scores`` the fp64 [dnc_iters, K] scores on the GPU and ``dnc.last_info``
+    ``{"removed": q, "power_iters": [...], "converged": [...]}`` per round."""
+    K, d = _robust_shape(wList, "dnc")
+    honest = _honest_size(options, "dnc")
+    iters, b, c, pit, ptol = _dnc_scalars(options)
+    f = K - honest
+    if honest < 1 or f < 0:
+        raise ValueError(f"dnc: honestSize {honest} not in [1, {K}]")
+    if not 2 <= K <= 4096:
+        raise ValueError(f"dnc: 2 <= K <= 4096 (got {K})")
+    q = int(c * f)
+    if q * iters >= K:
+        raise ValueError(f"dnc: q * dnc_iters = {q} * {iters} >= K = {K} rows would be removed")
+    cols = torch.empty(iters, 0, dtype=torch.int64)
+    if q > 0 and d > 0:
+        given = options.get("dnc_columns")
+        cols = (_dnc_given_columns(given, iters, d) if given is not None
+                else _dnc_draw(d, b, iters, options.get("generator")))
+        if K * cols.shape[1] > _DNC_MAX_ELEMS:
+            raise ValueError(f"dnc: K * n = {K} * {cols.shape[1]} sampled elements exceed 2^27: "
+                             "lower dnc_dims")
+    X, ldx, layout, K, d = _robust_operand(wList, "dnc")
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    scores = torch.zeros(iters, K, dtype=torch.float64, device=X.device)
+    good, n_good = (C.c_int32 * K)(*range(K)), C.c_int64(K)
+    nit, conv = (C.c_int32 * iters)(), (C.c_int32 * iters)(*([1] * iters))
+    if d > 0:
+        # (cdev goes back to torch's caching allocator, which reuses it in stream order)
+        cdev = cols.to(X.device) if q > 0 else None
+        context(X.device).call("gm_dnc_f32", X.data_ptr(), K, d, ldx, layout,
+                               cdev.data_ptr() if q > 0 else None, cols.shape[1], iters, q, pit,
+                               ptol, out.data_ptr(), scores.data_ptr(), good, C.byref(n_good), nit,
+                               conv, _stream_ptr(X.device))
+    dnc.last_columns = cols
+    dnc.last_selected = list(good[:n_good.value])
+    dnc.last_scores = scores
+    dnc.last_info = {"removed": q, "power_iters": list(nit), "converged": [bool(x) for x in conv]}
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+def _dnc_with_options(**fixed):
+    """An ``aggregate(wList, options)`` callable named "dnc" that applies the given dnc options
+    over the caller's, for loops that build the dict themselves
+    (training.run(..., aggregate=dnc.with_options(dnc_c=1.5, dnc_iters=3)))."""
+    unknown = sorted(set(fixed) - set(_DNC_KEYS))
+    if unknown:
+        raise TypeError(f"dnc.with_options takes {', '.join(_DNC_KEYS)} (got {unknown})")
+    _dnc_scalars(fixed)                                    # bad values fail here
+
+    def aggregate(wList, options={}):  # noqa: B006
+        return dnc(wList, {**(options or {}), **fixed})
+    aggregate.__name__ = aggregate.__qualname__ = "dnc"
+    aggregate.__doc__ = f"dnc with {fixed}"
+    return aggregate
+
+
+dnc.columns = _dnc_draw
+dnc.with_options = _dnc_with_options
+dnc.last_columns = dnc.last_selected = dnc.last_scores = dnc.last_info = None
 
 
 def honest_variance(w_local, honestSize: int) -> torch.Tensor:

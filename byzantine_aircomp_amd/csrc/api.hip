@@ -530,6 +530,111 @@ int gm_nnm_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int
   return GM_OK;
 }
 
+// GMAGG_DNC_STOP (read per call; tools/dnc_bench.py times the stages apart with it): 1 returns
+// after the first round's gather, 2 after the last round's selection (before the final mean);
+// anything else runs the whole call.
+static int dnc_stop() { return env_int("GMAGG_DNC_STOP", 0); }
+
+// The most elements of a sampled sub-matrix (512 MiB of workspace as fp32).
+constexpr int64_t kDncMaxElems = (int64_t)1 << 27;
+
+int gm_dnc_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+               const int64_t* columns, int64_t n, int64_t iters, int64_t remove,
+               int64_t power_iters, double power_tol, float* out, double* scores, int32_t* good,
+               int64_t* n_good, int32_t* niter, int32_t* converged, void* stream) {
+  if (!c || !X || !out || !scores || !good || !n_good || !niter || !converged ||
+      (remove > 0 && !columns))
+    return fail(GM_ERR_INVALID, "gm_dnc_f32: a NULL ctx, X, out, scores, good, n_good, niter or "
+                "converged, or NULL columns with remove > 0");
+  if (K < 2 || d < 0 || !known_layout(layout) || iters < 1 || remove < 0 || remove >= K ||
+      (remove > 0 && iters > (K - 1) / remove) || power_iters < 1 || !(power_tol >= 0) ||
+      (remove > 0 && (n < 1 || n > d)))
+    return fail(GM_ERR_INVALID, "gm_dnc_f32: bad args (K < 2, d < 0, an unknown layout, iters < 1, "
+                "remove < 0, remove * iters >= K, power_iters < 1, power_tol not >= 0, n outside "
+                "[1, d])");
+  if (K > 4096) return fail(GM_ERR_UNSUPPORTED, "gm_dnc_f32: K <= 4096 (got %lld)", (long long)K);
+  if (remove > 0 && n > kDncMaxElems / K)
+    return fail(GM_ERR_UNSUPPORTED, "gm_dnc_f32: K * n = %lld x %lld sampled elements exceed %lld",
+                (long long)K, (long long)n, (long long)kDncMaxElems);
+  int ws = 0;
+  int rc = robust_shift("gm_dnc_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (c->d_total > 0 || c->comm || c->ar_fn)
+    return fail(GM_ERR_UNSUPPORTED, "gm_dnc_f32: a d-sharded or collective context (the sampled "
+                "columns and the final mean would span the shards)");
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (remove == 0) {       // nothing is filtered: the column mean, gm_mean_f32's launch
+    HIPCHK(hipSetDevice(c->device));
+    if (d > 0) HIPCHK(launch_col_mean(X, K, d, ldx, out, s, ws));
+    HIPCHK(hipMemsetAsync(scores, 0, sizeof(double) * (size_t)(iters * K), s));
+    for (int64_t t = 0; t < iters; ++t) { niter[t] = 0; converged[t] = 1; }
+    for (int64_t k = 0; k < K; ++k) good[k] = (int32_t)k;
+    *n_good = K;
+    return GM_OK;
+  }
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  DncWork w{};
+  dnc_slices(K, n, &w.slices, &w.slice_rows);
+  int32_t *flag = nullptr, *goodf = nullptr, *list = nullptr;
+  auto lay = [&](char* base) {
+    Carve cv{base};
+    w.st = cv.take<DncState>(1);
+    w.G = cv.take<float>((size_t)(K * n));
+    w.mu = cv.take<double>(n);
+    w.v = cv.take<double>(n);
+    w.w = cv.take<double>(n);
+    w.part = cv.take<double>((size_t)(w.slices * n));
+    w.p = cv.take<double>(K);
+    w.bn = cv.take<double>(kDncBlocks);
+    w.bm = cv.take<double>(kDncBlocks);
+    flag = cv.take<int32_t>(K);
+    goodf = cv.take<int32_t>(K);
+    list = cv.take<int32_t>(K);
+    return cv.off;
+  };
+  rc = grow_ws(c, lay(nullptr));
+  if (rc) return rc;
+  lay(c->ws);
+  // the pinned buffer: DncState | pad to 256 | int32 flags[K]
+  rc = ensure_host(c, 256 + sizeof(int32_t) * (size_t)K);
+  if (rc) return rc;
+  DncState* hst = reinterpret_cast<DncState*>(c->host);
+  int32_t* hflag = reinterpret_cast<int32_t*>(c->host + 256);
+  const int stop = dnc_stop();
+  for (int64_t t = 0; t < iters; ++t) {
+    HIPCHK(launch_dnc_gather(X, K, ldx, ws, columns + t * n, n, w.G, s));
+    if (stop == 1) return GM_OK;
+    HIPCHK(launch_dnc_center(w, K, n, s));
+    HIPCHK(launch_dnc_start(w, K, n, s));
+    // the iteration runs ahead in chunks; the state is polled between them
+    for (int64_t it = 0; it < power_iters;) {
+      const int64_t chunk = std::min<int64_t>(it == 0 ? 8 : 16, power_iters - it);
+      HIPCHK(launch_dnc_iterate(w, K, n, power_tol, chunk, s));
+      it += chunk;
+      HIPCHK(hipMemcpyAsync(hst, w.st, sizeof(DncState), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (hst->done) break;
+    }
+    niter[t] = hst->iters;
+    converged[t] = hst->converged;
+    double* sc = scores + t * K;
+    HIPCHK(launch_dnc_scores(w, K, n, sc, s));
+    HIPCHK(launch_score_top_m(sc, K, K - remove, flag, s));
+    HIPCHK(launch_dnc_and_flags(goodf, flag, K, t == 0, s));
+  }
+  HIPCHK(launch_flags_to_list(goodf, K, 1, list, s));
+  HIPCHK(hipMemcpyAsync(hflag, goodf, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int64_t m = 0;
+  for (int64_t k = 0; k < K; ++k)
+    if (hflag[k]) good[m++] = (int32_t)k;
+  *n_good = m;                                       // >= K - remove * iters >= 1
+  if (stop == 2) return GM_OK;
+  HIPCHK(launch_gather_mean(X, d, ldx, ws, list, m, out, s));
+  return GM_OK;
+}
+
 int gm_oma_philox_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, double noise_var,
                       uint64_t seed, void* stream) {
   if (!c || !X || K < 0 || d < 0 || ldx < d || noise_var < 0)

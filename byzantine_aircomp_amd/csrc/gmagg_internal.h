@@ -308,6 +308,15 @@ hipError_t launch_meamed(const float* X, int64_t d, int64_t ldx, int ws, const i
 hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, const float* X,
                                   int64_t d, int64_t ldx, int ws, int32_t* flag, int32_t* list,
                                   float* out, hipStream_t s);
+// Its three steps, one launch each (the tail of DnC's rounds as well): flag[i] = 1 for the m rows
+// first in the order of scores; the indices with flag[i] == want, increasing -> list; the fp64
+// mean of rows list[0 .. m-1] in that order -> out.
+hipError_t launch_score_top_m(const double* score, int64_t K, int64_t m, int32_t* flag,
+                              hipStream_t s);
+hipError_t launch_flags_to_list(const int32_t* flag, int64_t K, int32_t want, int32_t* list,
+                                hipStream_t s);
+hipError_t launch_gather_mean(const float* X, int64_t d, int64_t ldx, int ws, const int32_t* list,
+                              int64_t m, float* out, hipStream_t s);
 // Bulyan's theta selection rounds on D [K][K] (upper triangle): order [theta] in selection
 // order, list [theta] the same rows increasing; score [K], ord [K][K] (each row's columns by
 // stable rank) and alive [K] are scratch.
@@ -383,6 +392,49 @@ hipError_t launch_nnm_neighbors(const double* D, int64_t K, int64_t m, uint32_t*
 hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
                           const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
                           hipStream_t s);
+// DnC's spectral part on the K x n sampled sub-matrix (dnc.hip; the definition is in
+// include/gmagg.h).  The sub-matrix is kept as the gathered fp32 values G [K][n] and the column
+// means mu [n]: a centred element is (double)G[k][j] - mu[j], formed where it is used.
+struct DncState {
+  int32_t done;         // the round's iteration has ended (later launches are no-ops)
+  int32_t converged;
+  int32_t iters;        // applications of C^T C
+  int32_t degenerate;   // a zero or non-finite norm: every score is val
+  int64_t kstar;        // the row the start vector is taken from
+  double val;
+  double movement;      // ||v_t - v_{t-1}|| of the last application
+};
+constexpr int kDncBlocks = 1024;      // most blocks of the n-space reductions (bn, bm entries)
+struct DncWork {
+  float* G;             // [K][n]
+  double* mu;           // [n]
+  double* v;            // [n] the unit iterate
+  double* w;            // [n] C^T C v
+  double* part;         // [slices][n] partial column sums of C^T p over row slices
+  double* p;            // [K] row norms^2, then C v
+  double* bn;           // [kDncBlocks] block partials of ||w||^2
+  double* bm;           // [kDncBlocks] block partials of ||v_t - v_{t-1}||^2
+  DncState* st;
+  int64_t slices, slice_rows;
+};
+// Row slices of the C^T p pass for a K x n sub-matrix (a function of K and n alone, so the
+// summation order, and with it every bit of the result, is too): slices = ceil(K / slice_rows).
+void dnc_slices(int64_t K, int64_t n, int64_t* slices, int64_t* slice_rows);
+// G[k][t] = X[k][cols[t]] (cols: device int64 [n], each in [0, d); not checked), then mu.
+hipError_t launch_dnc_gather(const float* X, int64_t K, int64_t ldx, int ws, const int64_t* cols,
+                             int64_t n, float* G, hipStream_t s);
+hipError_t launch_dnc_center(const DncWork& w, int64_t K, int64_t n, hipStream_t s);
+// The start vector (the centred row of largest norm, normalised) and the round's fresh state.
+hipError_t launch_dnc_start(const DncWork& w, int64_t K, int64_t n, hipStream_t s);
+// `count` applications v <- C^T C v / ||.|| with the movement test against tol; no-ops once
+// the state is done.
+hipError_t launch_dnc_iterate(const DncWork& w, int64_t K, int64_t n, double tol, int64_t count,
+                              hipStream_t s);
+// score[k] = (c_k . v)^2, or the state's val for every k after a degenerate norm.
+hipError_t launch_dnc_scores(const DncWork& w, int64_t K, int64_t n, double* score, hipStream_t s);
+// good[i] = flag[i] (first) or good[i] & flag[i].
+hipError_t launch_dnc_and_flags(int32_t* good, const int32_t* flag, int64_t K, bool first,
+                                hipStream_t s);
 // The omniscient attacks (attack.hip), in place: rows H .. K-1 of X are overwritten from the
 // statistics of rows 0 .. H-1; ws = log2 of the panel width (0: rows), ldx the row or panel
 // stride.  Any alignment (4-column vector items where the base and stride allow).

@@ -260,12 +260,29 @@ __global__ void __launch_bounds__(256) gather_mean(const float* __restrict__ X, 
   }
 }
 
+hipError_t launch_score_top_m(const double* score, int64_t K, int64_t m, int32_t* flag,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(score_top_m, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, score, K, m,
+                     flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_flags_to_list(const int32_t* flag, int64_t K, int32_t want, int32_t* list,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(flags_to_list, dim3(1), dim3(64), 0, s, flag, K, want, list);
+  return hipGetLastError();
+}
+
 hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, const float* X,
                                   int64_t d, int64_t ldx, int ws, int32_t* flag, int32_t* list,
                                   float* out, hipStream_t s) {
-  hipLaunchKernelGGL(score_top_m, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, score, K, m,
-                     flag);
-  hipLaunchKernelGGL(flags_to_list, dim3(1), dim3(64), 0, s, flag, K, 1, list);
+  (void)launch_score_top_m(score, K, m, flag, s);
+  (void)launch_flags_to_list(flag, K, 1, list, s);
+  return launch_gather_mean(X, d, ldx, ws, list, m, out, s);
+}
+
+hipError_t launch_gather_mean(const float* X, int64_t d, int64_t ldx, int ws, const int32_t* list,
+                              int64_t m, float* out, hipStream_t s) {
   if (d > 0) {
     const bool v4 = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 4 == 0 && d % 4 == 0;
     const int64_t items = v4 ? d / 4 : d;

@@ -466,6 +466,83 @@ int gm_nnm_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, i
                int64_t f, float* Y, int64_t ldy, int32_t layout_out, int32_t* neighbors,
                void* stream);
 
+/* Divide-and-Conquer, DnC (Shejwalkar & Houmansadr, "Manipulating the Byzantine: Optimizing Model
+ * Poisoning Attacks and Defenses for Federated Learning", NDSS 2021, Algorithm 2): spectral
+ * filtering on sampled coordinates, the defence the min-max / min-sum attacks above were
+ * published with.
+ *
+ * Inputs:
+ * - X, with K rows
+ * - f = K - honestSize
+ * - `iters` >= 1
+ * - `remove` = q >= 0 rows per round
+ * - per round t, a strictly increasing list J_t of n distinct columns, 1 <= n <= d
+ *
+ * Per round, all in fp64 on the fp32 values widened exactly:
+ *
+ * 1. mu_j = (sum_k x_kj) / K, summed in row order, for j in J_t.  c_kj = x_kj - mu_j.
+ * 2. v is the top right singular vector of C = (c_kj), found by power iteration on C^T C or,
+ *    equivalently, on C C^T.  Both are positive semidefinite, so the iterate never flips sign
+ *    and no sign alignment is needed.
+ *    - The start vector is yours to choose.  It must be deterministic and must not be the
+ *      all-ones vector in K-space: the columns are centred, so that vector lies in the null
+ *      space.  Document the choice.
+ *    - Stop when the unit iterate moves by ||u_t - u_{t-1}||_2 <= `power_tol` (default 1e-10)
+ *      or after `power_iters` (default 100) iterations.
+ *    - A zero or non-finite norm ends the round at once, with every score equal to that value
+ *      (0 or NaN).
+ * 3. s_k = (sum_j c_kj v_j)^2.
+ * 4. kept_t is the K - q rows first in the order (s ascending, NaN last, ties to the lower row
+ *    index).  This is score_before's order in robust.hip.
+ *
+ * Then good = the intersection of the kept_t.  For each column, out is the fp64 sum of the good
+ * rows in increasing row index, divided by |good| and rounded to fp32 once.  A single good row
+ * is returned as itself.  This is exactly what gather_mean does.
+ *
+ * With q = 0 there is no spectral work and no column draw.  The result is the column mean of
+ * all rows, bit for bit what `mean` returns.
+ *
+ * The result and every reported quantity are bit-identical for rows, panels and every
+ * alignment.  The gathered values are the same in each case, so this is required, not hoped
+ * for.
+ *
+ * The choices this implementation makes within that text:
+ *   iteration  on C^T C, in the n-space of the sampled columns: v_t = C^T (C v_{t-1}) / ||.||, one
+ *              "iteration" being one such application; the scores are (C v_t)^2 of the last
+ *              iterate, converged or not.
+ *   start      v_0 = c_r / ||c_r||, r the row of largest ||c_k||^2 (a NaN norm first, ties to
+ *              the lower index): a vector of C's row space, which a row that stands out dominates.
+ *              ||c_r|| zero or non-finite is the zero / non-finite norm of step 2 (all rows equal
+ *              on J_t: every score 0; a NaN in a sampled column: every score NaN; an infinite
+ *              norm scores +inf), with 0 iterations reported, converged = 1 for the zero norm
+ *              only.
+ *   sums       mu_j from 0.0 in row order; every other sum in a fixed order that depends on
+ *              (K, n) alone.
+ *
+ *   X          fp32, layout GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any alignment) or GM_LAYOUT_PANELS
+ *              ([ceil(d/W)][K][W], W = gm_panel_width(K), ldx = panel stride >= K*W).  Never
+ *              written; nothing at or past column d is read.
+ *   columns    device int64 [iters][n], row t = J_t.  NOT validated: an entry outside [0, d)
+ *              reads out of bounds.  Unused (may be NULL) when remove == 0.
+ *   out        device fp32 [d].
+ *   scores     device double [iters][K], round t's s_k (zeros when remove == 0).
+ *   good       host int32 [K]: the good rows, increasing, in its first *n_good entries.
+ *   niter, converged   host int32 [iters]: per round the iterations run and whether the movement
+ *              test passed.
+ * Uses the context's workspace (stream-ordered with the other calls on it): 4 K n bytes for the
+ * sub-matrix plus O(n + K).  With remove > 0 the call blocks until the stream has run the
+ * selection (the host reads the iteration's state and the good rows); the final mean is queued
+ * behind it.
+ * GM_ERR_INVALID (nothing written): a NULL pointer, K < 2, d < 0, an unknown layout, iters < 1,
+ * remove < 0, remove * iters >= K, power_iters < 1, power_tol not >= 0, a rows layout with
+ * ldx < d (a panel stride < K*W) and, with remove > 0, n < 1 or n > d.  GM_ERR_UNSUPPORTED (with a
+ * message): K > 4096, K * n > 2^27 sampled elements, a panel layout whose K has no panel width, a
+ * d-sharded or collective context. */
+int gm_dnc_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+               const int64_t* columns, int64_t n, int64_t iters, int64_t remove,
+               int64_t power_iters, double power_tol, float* out, double* scores, int32_t* good,
+               int64_t* n_good, int32_t* niter, int32_t* converged, void* stream);
+
 /* Omniscient model-poisoning attacks, in place on the client matrix: rows 0 .. H-1 (H = K - byz
  * >= 2) are the honest clients, rows H .. K-1 the Byzantine ones (the reference's
  * messages[-byzantinesize:]), which are overwritten with ONE malicious row computed from the
