@@ -120,6 +120,8 @@ SIGNATURES = [
     ("gm_dnc_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _I64, _I64, _I64,
                              C.c_double, _P, _P, C.POINTER(C.c_int32), C.POINTER(_I64),
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("gm_fltrust_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
+    ("gm_fltrust_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
     ("gm_oma_philox_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_double, C.c_uint64, _P]),
     ("gm_honest_variance_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("gm_honest_variance_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P]),

@@ -57,6 +57,10 @@ sample's top singular vector are largest are dropped (``int(dnc_c * f)`` per rou
 rounds) and the rest averaged; fp32 rows or panels and ``honestSize`` like ``Krum``;
 ``dnc.with_options(...)`` fixes its options; it works under ``bucketed`` and ``mixed`` and as a
 training loop's ``aggregate``.
+``fltrust(wList, options)`` is FLTrust (Cao, Fang, Liu & Gong, NDSS 2021): every row is scored by
+the cosine of its update with the server's own (``server_update``, or row ``server_row``), and
+the rows of positive score, rescaled to the server update's norm, are averaged with their scores
+as weights, in fp64; fp32 or bf16 rows or panels; ``fltrust.with_options(...)`` fixes the server.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -76,7 +80,7 @@ from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
-           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc"]
+           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc", "fltrust"]
 
 
 @dataclass
@@ -1040,6 +1044,150 @@ def _dnc_with_options(**fixed):
 dnc.columns = _dnc_draw
 dnc.with_options = _dnc_with_options
 dnc.last_columns = dnc.last_selected = dnc.last_scores = dnc.last_info = None
+
+
+_FLTRUST_KEYS = ("server_update", "server_row")
+_FLTRUST_MAX_K = 2048             # gm_fltrust_f32 / _bf16's cap on K
+
+
+def _fltrust_server(options, K=None, d=None):
+    """(server_update or None, server_row or -1) from the options: exactly one of the two,
+    server_row an int (not a bool or a float), in [0, K) when K is known, server_update a tensor
+    of d elements when d is known; TypeError / ValueError otherwise."""
+    su, sr = options.get("server_update"), options.get("server_row")
+    if (su is None) == (sr is None):
+        raise ValueError("fltrust needs exactly one of options['server_update'] (a [d] tensor) and "
+                         "options['server_row'] (a row of wList)")
+    if su is not None:
+        if not isinstance(su, torch.Tensor):
+            raise TypeError(f"fltrust: server_update must be a tensor (got {type(su).__name__})")
+        if su.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"fltrust: server_update must be fp32 or bf16 (got {su.dtype})")
+        if d is not None and su.numel() != d:
+            raise ValueError(f"server_update has {su.numel()} elements, wList rows have {d}")
+        return su, -1
+    try:
+        if isinstance(sr, bool):
+            raise TypeError
+        row = operator.index(sr)
+    except TypeError:
+        raise TypeError(f"fltrust: server_row must be an integer (got {sr!r})") from None
+    if row < 0 or (K is not None and row >= K):
+        raise ValueError(f"fltrust: server_row = {row} not in [0, {K if K is not None else 'K'})")
+    return None, row
+
+
+def _fltrust_shape(wList, who: str = "fltrust"):
+    """(K, d) of an fp32 or bf16 [K, d] tensor or ClientPanels, K in [1, 2048]; TypeError /
+    ValueError otherwise, before anything touches a GPU."""
+    if not isinstance(wList, ClientPanels) and (not isinstance(wList, torch.Tensor)
+                                                or wList.dim() != 2):
+        raise ValueError(f"{who}: wList must be a [K, d] tensor or ClientPanels")
+    if wList.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{who} reads fp32 or bf16 client updates (got {wList.dtype})")
+    K, d = (int(n) for n in wList.shape)
+    if K < 1:
+        raise ValueError(f"{who}: wList has no rows")
+    if K > _FLTRUST_MAX_K:
+        raise ValueError(f"{who}: K <= {_FLTRUST_MAX_K} (got {K})")
+    return K, d
+
+
+def _fltrust_vec(v, d: int, device, what: str):
+    """v as a contiguous fp32 [d] vector on `device` (None stays None)."""
+    if v is None:
+        return None
+    if v.numel() != d:
+        raise ValueError(f"{what} has {v.numel()} elements, wList rows have {d}")
+    return v.detach().reshape(-1).to(device=device, dtype=torch.float32).contiguous()
+
+
+def _run_fltrust(ctx, X, K: int, d: int, ldx: int, layout: int, server, row: int, centre):
+    """gm_fltrust_f32 / _bf16 on ctx: (out [d] fp32, stats [3K + 2] fp64) on X's device."""
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    stats = torch.zeros(3 * K + 2, dtype=torch.float64, device=X.device)
+    ctx.call("gm_fltrust_bf16" if X.dtype == torch.bfloat16 else "gm_fltrust_f32", X.data_ptr(),
+             K, d, ldx, layout, server.data_ptr() if server is not None else None, row,
+             centre.data_ptr() if centre is not None else None, out.data_ptr(), stats.data_ptr(),
+             _stream_ptr(X.device))
+    return out, stats
+
+
+def _fltrust_info(stats, K: int):
+    return {"cos": stats[:K], "norm2": stats[K:2 * K], "trust": stats[2 * K:3 * K],
+            "server_norm2": stats[3 * K], "trust_sum": stats[3 * K + 1]}
+
+
+def fltrust(wList, options):
+    """FLTrust (Cao, Fang, Liu & Gong, "FLTrust: Byzantine-robust Federated Learning via Trust
+    Bootstrapping", NDSS 2021), not one of the reference's aggregators: the server holds an
+    update of its own, every client is scored by the cosine of its update with the server's,
+    negative scores are cut to zero, and the clients of positive score, each rescaled to the
+    server update's norm, are averaged with their scores as weights.  With c = options['guess']
+    (default None: zeros, the rows are updates; the training loop passes the current model, so
+    the rows are models and c the model they started from), u_k = x_k - c and g = s - c:
+
+        TS_k = max(0, cos(u_k, g)),    out = c + sum_k TS_k ||g|| / ||u_k|| u_k / sum_k TS_k
+
+    in fp64 on the widened values, rounded once (the definition, the skipped rows and the order
+    of every sum are in include/gmagg.h).  A row of zero or non-finite norm, a row with a
+    non-finite product and the server row itself score 0 and are not read again; when no row is
+    trusted the result is c itself (the paper leaves that case undefined).
+
+    The server update s is given by exactly one of
+      ``server_update``  a [d] tensor (fp32 or bf16) in the rows' representation: a model when
+                         the rows are models, an update when they are updates;
+      ``server_row``     an int in [0, K): that row of wList is the server's (the client that
+                         trains on the root dataset); it gets no weight itself.  The index is into
+                         the rows the CALLER passes: under ``bucketed(...)`` / ``mixed(...)`` the
+                         rows are bucket means or mixed rows, and only ``server_update`` is
+                         meaningful.
+    Every other key (maxiter, tol, honestSize, noise_var, ...) is ignored.
+
+    wList: an fp32 or bf16 [K, d] tensor (any stride; a CPU tensor is staged to the GPU and the
+    result copied back) or an fp32 or bf16 ClientPanels, K <= 2048; never written.  fp16 / fp64
+    raise TypeError; K > 2048 and wrong lengths ValueError; all before a GPU is touched.  The
+    result is fp32 on wList.device.  Two HIP passes (fltrust.hip): one read of wList, one of the
+    trusted rows; no host synchronisation.  ``fltrust.last_info`` holds the by-products as views
+    of one device buffer: ``cos``, ``norm2`` (||u_k||^2) and ``trust`` (TS_k) as fp64 [K],
+    ``server_norm2`` and ``trust_sum`` as 0-dim tensors."""
+    options = options or {}
+    K, d = _fltrust_shape(wList)
+    su, row = _fltrust_server(options, K, d)
+    guess = options.get("guess")
+    if guess is not None and guess.numel() != d:
+        raise ValueError(f"guess has {guess.numel()} elements, wList rows have {d}")
+    if isinstance(wList, ClientPanels):
+        X, ldx, layout = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
+        layout = _lib.GM_LAYOUT_ROWS
+    server = _fltrust_vec(su, d, X.device, "server_update")
+    centre = _fltrust_vec(guess, d, X.device, "guess")
+    out, stats = _run_fltrust(context(X.device), X, K, d, ldx, layout, server, row, centre)
+    fltrust.last_info = _fltrust_info(stats, K)
+    return out if wList.device == out.device else out.to(wList.device)
+
+
+def _fltrust_with_options(**fixed):
+    """An ``aggregate(wList, options)`` callable named "fltrust" that applies server_update /
+    server_row over the caller's options, for loops that build the dict themselves
+    (training.run(..., aggregate=fltrust.with_options(server_row=0)): client 0's shard is the
+    root dataset)."""
+    unknown = sorted(set(fixed) - set(_FLTRUST_KEYS))
+    if unknown:
+        raise TypeError(f"fltrust.with_options takes {', '.join(_FLTRUST_KEYS)} (got {unknown})")
+    _fltrust_server(fixed)                                 # bad values fail here
+
+    def aggregate(wList, options={}):  # noqa: B006
+        return fltrust(wList, {**(options or {}), **fixed})
+    aggregate.__name__ = aggregate.__qualname__ = "fltrust"
+    aggregate.__doc__ = f"fltrust with {sorted(fixed)}"
+    return aggregate
+
+
+fltrust.with_options = _fltrust_with_options
+fltrust.last_info = None
 
 
 def honest_variance(w_local, honestSize: int) -> torch.Tensor:

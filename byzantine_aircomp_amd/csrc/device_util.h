@@ -80,8 +80,9 @@ template <> struct ilog2<1> { static constexpr int v = 0; };
 // lane bit and adds the partner's other half), then plain butterflies over
 // any lane bits left.  Afterwards lane c holds RPL = max(1, R/LPR) row sums in
 // e[0..RPL); slot m is row row_of_lane<LPR,R>(c) + m.  ~R shuffles for R rows.
-template <int LPR, int R>
-__device__ __forceinline__ void transpose_reduce(float (&e)[R], int c) {
+// (T: float, or double as in fltrust.hip's pass A)
+template <int LPR, int R, class T>
+__device__ __forceinline__ void transpose_reduce(T (&e)[R], int c) {
   constexpr int STEPS = cmin<ilog2<R>::v, ilog2<LPR>::v>::v;
 #pragma unroll
   for (int step = 0; step < STEPS; ++step) {
@@ -90,8 +91,8 @@ __device__ __forceinline__ void transpose_reduce(float (&e)[R], int c) {
     const bool up = (c & o) != 0;
 #pragma unroll
     for (int i = 0; i < half; ++i) {
-      float keep = up ? e[i + half] : e[i];
-      float send = up ? e[i] : e[i + half];
+      T keep = up ? e[i + half] : e[i];
+      T send = up ? e[i] : e[i + half];
       e[i] = keep + __shfl_xor(send, o, 64);
     }
   }

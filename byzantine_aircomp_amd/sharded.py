@@ -23,8 +23,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .aggregators import (GMResult, Context, _cclip_params, _gm_opts, _noise_source, _result,
-                          _run_cclip, _stream_ptr)
+from .aggregators import (GMResult, Context, _cclip_params, _fltrust_info, _fltrust_server,
+                          _fltrust_shape, _fltrust_vec, _gm_opts, _noise_source, _result,
+                          _run_cclip, _run_fltrust, _stream_ptr)
 from .panels import ClientPanels
 
 __all__ = ["shard_range", "ShardedGM", "torch_allreduce_adapter"]
@@ -90,7 +91,7 @@ def _aligned(shards, d_total: int) -> bool:
 
 
 class ShardedGM:
-    """gm2 / gm / cclip on this rank's column shard of a d_total-long update."""
+    """gm2 / gm / cclip / fltrust on this rank's column shard of a d_total-long update."""
 
     def __init__(self, d_total: int, group=None, device: torch.device | None = None,
                  transport: str = "rccl", shard: tuple[int, int] | None = None):
@@ -132,6 +133,7 @@ class ShardedGM:
         else:
             raise ValueError(f"transport must be 'rccl' or 'torch' (got {transport!r})")
         self.last_result: GMResult | None = None
+        self.last_info: dict | None = None     # fltrust's by-products
 
     @property
     def d_local(self) -> int:
@@ -199,6 +201,29 @@ class ShardedGM:
             raise ValueError(f"guess has {g0.numel()} elements, this shard has {self.d_local}")
         out, self.last_result, self.last_clipped = _run_cclip(
             self.ctx, ptr, False, X.shape[0], self.d_local, ldx, layout, g0, params)
+        return out
+
+    def fltrust(self, X, options):
+        """FLTrust (aggregators.fltrust) on this rank's fp32 [K, d_local] columns, rows or
+        ClientPanels: ``server_update`` and ``guess`` (None: zeros) are this rank's shards,
+        ``server_row`` a row of X, identical on every rank.  The 2K + 1 fp64 sums are
+        all-reduced once; every rank derives the same trust scores and coefficients
+        (``last_info``, as ``fltrust.last_info``, holds the same bits on every rank)."""
+        options = options or {}
+        K, _ = _fltrust_shape(X, "ShardedGM.fltrust")
+        if X.dtype != torch.float32:
+            raise TypeError(f"ShardedGM.fltrust reads fp32 shards (got {X.dtype})")
+        su, row = _fltrust_server(options, K, self.d_local)
+        guess = options.get("guess")
+        if guess is not None and guess.numel() != self.d_local:
+            raise ValueError(f"guess has {guess.numel()} elements, this shard has {self.d_local}")
+        X, ptr, ldx, layout = self._operand(X)
+        data = X.data if isinstance(X, ClientPanels) else X
+        server = _fltrust_vec(su, self.d_local, self.device, "server_update")
+        centre = _fltrust_vec(guess, self.d_local, self.device, "guess")
+        out, stats = _run_fltrust(self.ctx, data, K, self.d_local, ldx, layout, server, row,
+                                  centre)
+        self.last_info = _fltrust_info(stats, K)
         return out
 
     def gm2(self, X, options=None):

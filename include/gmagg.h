@@ -543,6 +543,63 @@ int gm_dnc_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, i
                int64_t power_iters, double power_tol, float* out, double* scores, int32_t* good,
                int64_t* n_good, int32_t* niter, int32_t* converged, void* stream);
 
+/* FLTrust (Cao, Fang, Liu & Gong, "FLTrust: Byzantine-robust Federated Learning via Trust
+ * Bootstrapping", NDSS 2021): the only rule here that scores a client against a reference vector,
+ * the server's own update, instead of against the other clients.
+ *
+ * Inputs:
+ * - rows x_k, k < K
+ * - the server vector s: `server` [d], or row `server_row` of X (exactly one of the two;
+ *   server_row = -1 with a vector)
+ * - a centre c [d]; NULL is zeros, and the rows are then the updates themselves
+ *
+ * All arithmetic is fp64 on the fp32 / bf16 values widened exactly:
+ *
+ *     u_k = x_k - c                      g = s - c
+ *     a_k = sum_j u_kj g_j               n_k = sum_j u_kj^2        n_g = sum_j g_j^2
+ *     counted_k = (k != server_row) and n_g finite and n_g > 0
+ *                 and n_k finite and n_k > 0 and a_k finite
+ *     cos_k = a_k / sqrt(n_k n_g)
+ *     TS_k  = counted_k ? max(0, cos_k) : 0
+ *     T     = sum_k TS_k                 (increasing k)
+ *     coef_k = TS_k * sqrt(n_g / n_k) / T
+ *     out_j = float( c_j + sum_{k : TS_k > 0, increasing k} coef_k u_kj )     (rounded once)
+ *     T == 0:  out_j = c_j exactly  (zeros without a centre)
+ *
+ * The paper leaves T == 0 undefined; this build returns the centre.  A row with TS_k = 0 is
+ * skipped, not multiplied by zero: whatever it holds (inf, NaN, 1e38) contributes nothing, and
+ * the second pass does not read it.
+ *
+ * Two calls on the same input on the same device return the same bits.  Rows and panels agree to
+ * rounding, not bit for bit (the order of the row sums differs); given equal coefficients the
+ * sum over k is in increasing k in every layout.
+ *
+ *   X        fp32 (gm_fltrust_f32) or bfloat16 bit patterns (gm_fltrust_bf16); layout
+ *            GM_LAYOUT_ROWS ([K][ldx], any ldx >= d, any alignment: 16-byte loads where the base
+ *            and ldx allow, else one element at a time) or GM_LAYOUT_PANELS ([ceil(d/W)][K][W],
+ *            W = gm_panel_width(K) resp. gm_panel_width_bf16(K), ldx = panel stride >= K*W).
+ *            Never written; nothing at or past column d is read.
+ *   server, centre, out   device fp32 [d]; out aliases nothing.
+ *   stats    device double [3K + 2], or NULL: cos_k exactly as computed (IEEE NaN / inf where
+ *            undefined; the server row's own is about 1), then n_k, then TS_k, then n_g and T.
+ * Two passes over X on the context's workspace (stream-ordered with the other calls on it): one
+ * read of all K rows for the sums, one of the rows with TS_k > 0 for the result.  On an
+ * unsharded context the call makes no host synchronisation and no device-to-host copy: the
+ * number of trusted rows and T == 0 are read on the device by the second pass.
+ * On a d-sharded context (gm_ctx_set_shard plus an all-reduce) X, server, centre and out are this
+ * rank's columns; the 2K + 1 fp64 sums go through the all-reduce once, between the first pass and
+ * the K-space step, and every rank derives identical coefficients (identical stats bits).
+ * GM_ERR_INVALID (nothing written): a NULL ctx, X or out, K < 1, d < 0, an unknown layout, ldx < d
+ * (a panel stride < K*W), both or neither of server / server_row, server_row outside [0, K).
+ * GM_ERR_UNSUPPORTED (with a message): K > 2048, a panel layout whose K has no panel width.
+ * d == 0 returns GM_OK and launches nothing. */
+int gm_fltrust_f32 (gm_ctx* ctx, const float*    X, int64_t K, int64_t d, int64_t ldx,
+                    int32_t layout, const float* server, int64_t server_row, const float* centre,
+                    float* out, double* stats, void* stream);
+int gm_fltrust_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                    int32_t layout, const float* server, int64_t server_row, const float* centre,
+                    float* out, double* stats, void* stream);
+
 /* Omniscient model-poisoning attacks, in place on the client matrix: rows 0 .. H-1 (H = K - byz
  * >= 2) are the honest clients, rows H .. K-1 the Byzantine ones (the reference's
  * messages[-byzantinesize:]), which are overwritten with ONE malicious row computed from the
