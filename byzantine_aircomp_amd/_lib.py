@@ -22,6 +22,7 @@ GM_LAYOUT_ROWS, GM_LAYOUT_PANELS = 0, 1
 GM_GUARD_NONE, GM_GUARD_ACCEPTED, GM_GUARD_REJECTED, GM_GUARD_ACCEPTED_FLOOR = 0, 1, 2, 3
 GM_EXCHANGE_NONE, GM_EXCHANGE_AGENT, GM_EXCHANGE_XCD_LOCAL, GM_EXCHANGE_XCD_HIER = 0, 1, 2, 3
 GM_EXCHANGE_XCD_SPLIT = 4
+GM_CLIP_STATIC, GM_CLIP_ARC = 0, 1
 
 NOISE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_float),
                        C.POINTER(C.c_float), C.POINTER(C.c_float))
@@ -122,6 +123,10 @@ SIGNATURES = [
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     ("gm_fltrust_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
     ("gm_fltrust_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
+    ("gm_clip_rows_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, C.c_int32, _I64,
+                                   C.c_double, _P, _I64, C.c_int32, _P, _P]),
+    ("gm_clip_rows_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, C.c_int32, _I64,
+                                    C.c_double, _P, _I64, C.c_int32, _P, _P]),
     ("gm_oma_philox_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_double, C.c_uint64, _P]),
     ("gm_honest_variance_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("gm_honest_variance_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P]),

@@ -61,6 +61,10 @@ training loop's ``aggregate``.
 the cosine of its update with the server's own (``server_update``, or row ``server_row``), and
 the rows of positive score, rescaled to the server update's norm, are averaged with their scores
 as weights, in fp64; fp32 or bf16 rows or panels; ``fltrust.with_options(...)`` fixes the server.
+``clip(wList, tau)`` and ``arc(wList, f)`` are norm clipping about a centre, static (Sun et al.
+2019) and adaptive (ARC, Allouah et al., ICLR 2025): the updates longer than the radius scaled
+back to it, in fp64; fp32 or bf16 rows or panels in, fp32 out, or fp32 in place;
+``clipped(aggregate)`` wraps any aggregator above with it, the centre being ``options['guess']``.
 
 There is no CPU path: without a GPU or without libgmagg.so these raise.
 """
@@ -80,7 +84,8 @@ from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
-           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc", "fltrust"]
+           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc", "fltrust", "clip", "arc",
+           "clipped"]
 
 
 @dataclass
@@ -1188,6 +1193,196 @@ def _fltrust_with_options(**fixed):
 
 fltrust.with_options = _fltrust_with_options
 fltrust.last_info = None
+
+
+_CLIP_MAX_K = 4096                # gm_clip_rows_f32 / _bf16's cap on K
+
+
+def _clip_shape(wList, who: str):
+    """(K, d) of an fp32 or bf16 [K, d] tensor or ClientPanels, K in [1, 4096]; TypeError /
+    ValueError otherwise, before anything touches a GPU."""
+    if not isinstance(wList, ClientPanels) and (not isinstance(wList, torch.Tensor)
+                                                or wList.dim() != 2):
+        raise ValueError(f"{who}: wList must be a [K, d] tensor or ClientPanels")
+    if wList.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{who} reads fp32 or bf16 client updates (got {wList.dtype})")
+    K, d = (int(n) for n in wList.shape)
+    if K < 1:
+        raise ValueError(f"{who}: wList has no rows")
+    if K > _CLIP_MAX_K:
+        raise ValueError(f"{who}: K <= {_CLIP_MAX_K} (got {K})")
+    return K, d
+
+
+def _clip_tau(tau, who: str) -> float:
+    """tau as a float > 0 (+inf allowed); ValueError otherwise (a bool, a string, 0, NaN)."""
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not tau > 0:
+        raise ValueError(f"{who}: tau must be a number > 0 (got {tau!r})")
+    return float(tau)
+
+
+def _clip_centre(centre, d: int, who: str):
+    """The centre as given (None, or an fp32 / bf16 tensor of d elements); TypeError /
+    ValueError otherwise."""
+    if centre is None:
+        return None
+    if not isinstance(centre, torch.Tensor):
+        raise TypeError(f"{who}: centre must be a tensor (got {type(centre).__name__})")
+    if centre.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{who}: centre must be fp32 or bf16 (got {centre.dtype})")
+    if centre.numel() != d:
+        raise ValueError(f"{who}: centre has {centre.numel()} elements, wList rows have {d}")
+    return centre
+
+
+def _clip_info(stats, K: int):
+    return {"norm2": stats[:K], "scale": stats[K:2 * K], "threshold2": stats[2 * K],
+            "clipped": stats[2 * K + 1]}
+
+
+def _run_clip(ctx, X, K: int, d: int, ldx: int, lin: int, centre, rule: int, f: int, tau: float,
+              panels_out: bool, inplace: bool = False):
+    """gm_clip_rows_f32 / _bf16 on ctx: (the clipped rows, stats [2K + 2] fp64) on X's device.
+    The rows are a [K, d] tensor or ClientPanels(K, d), or None in place (X holds them)."""
+    if inplace:
+        out, Y, ldy, lout = None, X, ldx, lin
+    elif panels_out:
+        out = ClientPanels(K, d, device=X.device, zero=False)    # every column < d is written
+        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        out = Y = torch.empty(K, d, dtype=torch.float32, device=X.device)
+        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    stats = torch.zeros(2 * K + 2, dtype=torch.float64, device=X.device)
+    if d > 0:
+        ctx.call("gm_clip_rows_bf16" if X.dtype == torch.bfloat16 else "gm_clip_rows_f32",
+                 X.data_ptr(), K, d, ldx, lin, centre.data_ptr() if centre is not None else None,
+                 rule, f, tau, Y.data_ptr(), ldy, lout, stats.data_ptr(), _stream_ptr(X.device))
+    else:                                # every n_k is 0: nothing to clip
+        stats[K:2 * K] = 1.0
+        stats[2 * K] = tau * tau if rule == _lib.GM_CLIP_STATIC else 0.0
+    return out, stats
+
+
+def _clip(fn, wList, rule: int, f, tau, centre, layout, inplace: bool):
+    who = fn.__name__
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"{who}: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    K, d = _clip_shape(wList, who)
+    if rule == _lib.GM_CLIP_ARC:
+        f, tau = _nnm_f(f, K, who), 0.0
+    else:
+        f, tau = 0, _clip_tau(tau, who)
+    centre = _clip_centre(centre, d, who)
+    panels_in = isinstance(wList, ClientPanels)
+    panels_out = layout == "panels" or (layout is None and panels_in)
+    if inplace:
+        if wList.dtype != torch.float32:
+            raise TypeError(f"{who}: inplace=True needs fp32 rows (got {wList.dtype}: the "
+                            "clipped rows are fp32)")
+        if panels_out != panels_in:
+            raise ValueError(f"{who}: inplace=True keeps wList's own layout (got {layout!r})")
+    elif panels_out and not _has_panels(K):
+        raise ValueError(f"{who}: no panel layout for K = {K} rows (take them row-major)")
+    if panels_in:
+        X, ldx, lin = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
+    else:
+        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
+        lin = _lib.GM_LAYOUT_ROWS
+    c = _fltrust_vec(centre, d, X.device, "centre")
+    out, stats = _run_clip(context(X.device), X, K, d, ldx, lin, c, rule, f, tau, panels_out,
+                           inplace)
+    fn.last_info = _clip_info(stats, K)
+    if inplace:
+        if not panels_in and X is not wList:
+            wList.copy_(X)               # (a CPU or non-unit-stride wList was clipped in a copy)
+        return wList
+    if isinstance(out, torch.Tensor) and wList.device != out.device:
+        out = out.to(wList.device)
+    return out
+
+
+def clip(wList, tau, centre=None, layout=None, inplace=False):
+    """Static norm clipping (Sun, Kairouz, Suresh & McMahan 2019), the pre-step that bounds what
+    one client can move: every row's update about `centre` longer than tau is scaled back to
+    length tau.  With c = centre (None: zeros, the rows are updates; a training loop's rows are
+    models and c is the model they started from) and u_k = x_k - c:
+
+        y_k = c + min(1, tau / ||u_k||) u_k
+
+    in fp64 on the widened values, rounded once; a row inside the radius is copied bit for bit,
+    a row whose norm is not finite becomes c itself (the definition is in include/gmagg.h).
+    Two HIP passes (clip.hip): one read of wList for the norms, one that writes the rows; no
+    host synchronisation.
+
+    wList: an fp32 or bf16 [K, d] tensor (any stride or alignment; a CPU tensor is staged to the
+    GPU and the row-major result copied back) or an fp32 or bf16 ClientPanels, K <= 4096.
+    tau: a number > 0 (``math.inf`` clips nothing finite).  Returns the clipped rows as fp32:
+    with ``layout=None`` a [K, d] tensor for a tensor and ``ClientPanels(K, d)`` for
+    ClientPanels; ``"rows"`` / ``"panels"`` force one.  ``inplace=True`` (fp32 only, wList's own
+    layout) overwrites the clipped rows of wList, leaves the others untouched and returns wList
+    itself; otherwise wList is never written.  fp16 / fp64 and bf16 in place raise TypeError;
+    K > 4096, a bad tau and wrong lengths ValueError; all before a GPU is touched.
+    ``clip.last_info`` holds the by-products as views of one device buffer: ``norm2``
+    (||u_k||^2) and ``scale`` (s_k) as fp64 [K], ``threshold2`` (tau^2) and ``clipped`` (the
+    number of rows with s_k != 1) as 0-dim tensors."""
+    return _clip(clip, wList, _lib.GM_CLIP_STATIC, None, tau, centre, layout, inplace)
+
+
+def arc(wList, f, centre=None, layout=None, inplace=False):
+    """Adaptive Robust Clipping, ARC (Allouah, Guerraoui, Gupta, Jellouli, Rizk & Stephan,
+    "Adaptive Gradient Clipping for Robust Federated Learning", ICLR 2025): ``clip`` with the
+    radius taken from the rows themselves.  With k = (2 f (K - f)) // K, the k updates of largest
+    norm about `centre` are scaled back to the norm of the (k + 1)-th largest; ties at the
+    threshold stay unclipped, a NaN norm ranks largest and its row becomes the centre.  Meant to
+    be composed with ``nnm`` and any aggregator (``clipped``, ``mixed``).
+
+    f: an integer in [0, K - 1], the number of Byzantine clients to clip against (``f == 0``
+    clips nothing finite).  Everything else as ``clip``; ``arc.last_info`` likewise, with
+    ``threshold2`` the squared radius chosen."""
+    return _clip(arc, wList, _lib.GM_CLIP_ARC, f, None, centre, layout, inplace)
+
+
+clip.last_info = arc.last_info = None
+
+
+def clipped(aggregate, tau=None, f=None, layout="panels"):
+    """An ``aggregate(wList, options)`` callable that clips wList about ``options.get('guess')``
+    (the current model in a training loop; None: zeros) and calls `aggregate` on the clipped
+    rows, handed over in `layout` ("panels" — rows where K has no panel width — "rows", or None
+    for wList's own).  tau None: ARC (``arc``), named ``f"{aggregate.__name__}_arc"``, with f the
+    number of Byzantine clients, None taking ``K - options['honestSize']`` per call (ValueError
+    without it); tau given: static clipping (``clip``), named ``f"{aggregate.__name__}_clip"``.
+    Works with every aggregator ``bucketed`` lists, under ``mixed(...)`` and ``bucketed(...)``,
+    and as ``training.run(..., aggregate=clipped(gm2))``.
+
+    Options pass through unchanged (clipping keeps all K rows, so ``honestSize`` stands); the
+    caller's dict and wList are not modified.  The result lives on wList.device, as the
+    aggregators' own."""
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"clipped: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    if tau is not None:
+        if f is not None:
+            raise ValueError("clipped takes tau (static clipping) or f (ARC), not both")
+        tau = _clip_tau(tau, "clipped")
+
+    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+        K = int(wList.shape[0])
+        centre = options.get("guess") if options else None
+        lay = "rows" if layout == "panels" and K >= 1 and not _has_panels(K) else layout
+        if tau is not None:
+            rows = clip(wList, tau, centre=centre, layout=lay)
+        else:
+            f_ = f if f is not None else K - _honest_size(options, agg.__name__)
+            rows = arc(wList, f_, centre=centre, layout=lay)
+        out = aggregate(rows, options)
+        if isinstance(out, torch.Tensor) and out.device != wList.device:
+            out = out.to(wList.device)        # (a CPU wList's clipped rows stayed on the GPU as panels)
+        return out
+
+    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_{'arc' if tau is None else 'clip'}"
+    agg.__doc__ = (f"{aggregate.__name__} on the rows clipped about options['guess'] "
+                   f"({'ARC' if tau is None else f'radius {tau}'})")
+    return agg
 
 
 def honest_variance(w_local, honestSize: int) -> torch.Tensor:

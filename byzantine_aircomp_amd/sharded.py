@@ -23,9 +23,10 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .aggregators import (GMResult, Context, _cclip_params, _fltrust_info, _fltrust_server,
-                          _fltrust_shape, _fltrust_vec, _gm_opts, _noise_source, _result,
-                          _run_cclip, _run_fltrust, _stream_ptr)
+from .aggregators import (GMResult, Context, _cclip_params, _clip_centre, _clip_info, _clip_shape,
+                          _clip_tau, _fltrust_info, _fltrust_server, _fltrust_shape, _fltrust_vec,
+                          _gm_opts, _nnm_f, _noise_source, _result, _run_cclip, _run_clip,
+                          _run_fltrust, _stream_ptr)
 from .panels import ClientPanels
 
 __all__ = ["shard_range", "ShardedGM", "torch_allreduce_adapter"]
@@ -91,7 +92,8 @@ def _aligned(shards, d_total: int) -> bool:
 
 
 class ShardedGM:
-    """gm2 / gm / cclip / fltrust on this rank's column shard of a d_total-long update."""
+    """gm2 / gm / cclip / fltrust / arc / clip on this rank's column shard of a d_total-long
+    update."""
 
     def __init__(self, d_total: int, group=None, device: torch.device | None = None,
                  transport: str = "rccl", shard: tuple[int, int] | None = None):
@@ -133,7 +135,7 @@ class ShardedGM:
         else:
             raise ValueError(f"transport must be 'rccl' or 'torch' (got {transport!r})")
         self.last_result: GMResult | None = None
-        self.last_info: dict | None = None     # fltrust's by-products
+        self.last_info: dict | None = None     # fltrust's, arc's or clip's by-products
 
     @property
     def d_local(self) -> int:
@@ -225,6 +227,36 @@ class ShardedGM:
                                   centre)
         self.last_info = _fltrust_info(stats, K)
         return out
+
+    def _clip(self, who, X, rule, f, tau, centre):
+        K, _ = _clip_shape(X, who)
+        if X.dtype != torch.float32:
+            raise TypeError(f"{who} reads fp32 shards (got {X.dtype})")
+        if rule == _lib.GM_CLIP_ARC:
+            f, tau = _nnm_f(f, K, who), 0.0
+        else:
+            f, tau = 0, _clip_tau(tau, who)
+        centre = _clip_centre(centre, self.d_local, who)
+        X, ptr, ldx, layout = self._operand(X)
+        panels = isinstance(X, ClientPanels)
+        out, stats = _run_clip(self.ctx, X.data if panels else X, K, self.d_local, ldx, layout,
+                               _fltrust_vec(centre, self.d_local, self.device, "centre"), rule, f,
+                               tau, panels)
+        self.last_info = _clip_info(stats, K)
+        return out
+
+    def arc(self, X, f, centre=None):
+        """ARC (aggregators.arc) on this rank's fp32 [K, d_local] columns, rows or ClientPanels:
+        `centre` (None: zeros) is this rank's shard, f identical on every rank.  The K fp64
+        squared norms are all-reduced once; every rank derives the same threshold and scales
+        (``last_info``, as ``arc.last_info``, holds the same bits on every rank).  Returns this
+        rank's columns of the clipped rows, in X's layout."""
+        return self._clip("ShardedGM.arc", X, _lib.GM_CLIP_ARC, f, None, centre)
+
+    def clip(self, X, tau, centre=None):
+        """Static clipping (aggregators.clip) to the radius tau of the whole d_total-long
+        update, on this rank's columns; as ``arc``."""
+        return self._clip("ShardedGM.clip", X, _lib.GM_CLIP_STATIC, None, tau, centre)
 
     def gm2(self, X, options=None):
         """X: this rank's [K, d_local] columns, as a tensor or a ClientPanels."""

@@ -600,6 +600,77 @@ int gm_fltrust_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_
                     int32_t layout, const float* server, int64_t server_row, const float* centre,
                     float* out, double* stats, void* stream);
 
+/* Norm clipping ahead of every aggregator above: static clipping (Sun, Kairouz, Suresh & McMahan,
+ * "Can You Really Backdoor Federated Learning?", 2019) and its adaptive form ARC, Adaptive Robust
+ * Clipping (Allouah, Guerraoui, Gupta, Jellouli, Rizk & Stephan, "Adaptive Gradient Clipping for
+ * Robust Federated Learning", ICLR 2025): every row's update about a centre is scaled back to a
+ * radius, a given one or the norm of the (k + 1)-th largest update.  Y has K rows.
+ *
+ * Inputs:
+ * - rows x_k, k < K
+ * - a centre c [d]; NULL is zeros, and the rows are then the updates themselves
+ * - a rule: GM_CLIP_STATIC with tau > 0, or GM_CLIP_ARC with 0 <= f <= K - 1
+ *
+ * All arithmetic is fp64 on the fp32 / bf16 values widened exactly:
+ *
+ *     u_kj = x_kj - c_j                  n_k = sum_j u_kj^2
+ *     ARC(f):      k = (2 f (K - f)) div K       (integer arithmetic; f <= K - 1, so k <= K/2)
+ *                  T = the n at zero-based rank K - 1 - k in the order of score_before
+ *                      (robust.hip: ascending, NaN last, ties to the lower index): the (k + 1)-th
+ *                      largest n_k, with NaN ranked largest.  sqrt(T) is the paper's radius C.
+ *     static(tau): T = (double)tau * (double)tau    (tau = +inf: nothing finite is clipped)
+ *     s_k = 0                 if n_k is NaN or +inf
+ *           1                 else if T is NaN or n_k <= T
+ *           sqrt(T / n_k)     otherwise
+ *     y_kj = x_kj widened, the same value (-0 stays -0)   if s_k == 1  (a copy, not an evaluation)
+ *            c_j exactly (zeros without a centre)         if s_k == 0  (the row is not read again)
+ *            float(c_j + s_k u_kj), rounded once          otherwise
+ *
+ * k is computed in integer arithmetic.  The floating-point evaluation int(2 * (f / K) * (K - f))
+ * found elsewhere differs from it: of the pairs with K <= 4096 and f < K/2, 80 disagree, the
+ * first at (K, f) = (242, 33), where the exact value is 57 and the float form gives 56.
+ * The order of each n_k sum depends on (d, layout, load path) only and is the same for every
+ * row, so rows that hold equal values have equal n_k bits, and a tie at the threshold leaves
+ * both rows unclipped, deterministically.  A row whose norm is not finite maps to the centre (a
+ * zero update; the paper leaves it undefined): like FLTrust's rows of zero trust it is skipped,
+ * not multiplied by zero, and the second pass does not read it.
+ *
+ *   X        fp32 (gm_clip_rows_f32) or bfloat16 bit patterns (gm_clip_rows_bf16); layout_in
+ *            GM_LAYOUT_ROWS ([K][ldx], any ldx >= d, any alignment: 16-byte loads where the base
+ *            and ldx allow, else one element at a time) or GM_LAYOUT_PANELS ([ceil(d/W)][K][W],
+ *            W = gm_panel_width(K) resp. gm_panel_width_bf16(K), ldx = panel stride >= K*W).
+ *            Nothing at or past column d is read.
+ *   Y        fp32, layout_out likewise with ldy and W = gm_panel_width(K); columns >= d are not
+ *            written.  Out of place, Y overlaps no byte of X; X is not written, every row with
+ *            s_k != 0 is read and all K rows are written.  In place, Y is X exactly (the same
+ *            pointer, stride and layout; fp32 only): the rows with 0 < s_k < 1 are read, and only
+ *            the rows with s_k != 1 are written.
+ *   centre   device fp32 [d], or NULL.
+ *   stats    device double [2K + 2], or NULL: n_k, then s_k, then T and the number of rows with
+ *            s_k != 1.
+ * Two passes over X on the context's workspace (stream-ordered with the other calls on it).  On
+ * an unsharded context the call makes no host synchronisation and no device-to-host copy: the
+ * second pass takes its row list and count from device memory.  Two calls on the same input on
+ * the same device return the same bits; rows-out and panels-out hold the same bits for the same
+ * input; input layouts agree to rounding (the order of the n_k sums differs).
+ * On a d-sharded context (gm_ctx_set_shard plus an all-reduce) X, centre and Y are this rank's
+ * columns; the K fp64 sums n_k go through the all-reduce once, between the first pass and the
+ * K-space step, and every rank derives identical T and s_k (identical stats bits).
+ * GM_ERR_INVALID (nothing written): a NULL ctx, X or Y, K < 1, d < 0, an unknown rule or layout,
+ * ldx or ldy too small for its layout, f outside [0, K - 1] (ARC), tau not > 0 (static), Y
+ * overlapping X other than as in place.  GM_ERR_UNSUPPORTED (with a message): K > 4096, a panel
+ * layout whose K has no panel width, bf16 in place.  d == 0 returns GM_OK before any device call. */
+typedef enum gm_clip_rule {
+    GM_CLIP_STATIC = 0,       /* the radius tau */
+    GM_CLIP_ARC = 1           /* the radius from the rows' own norms and f */
+} gm_clip_rule;
+int gm_clip_rows_f32 (gm_ctx* ctx, const float*    X, int64_t K, int64_t d, int64_t ldx,
+                      int32_t layout_in, const float* centre, int32_t rule, int64_t f, double tau,
+                      float* Y, int64_t ldy, int32_t layout_out, double* stats, void* stream);
+int gm_clip_rows_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                      int32_t layout_in, const float* centre, int32_t rule, int64_t f, double tau,
+                      float* Y, int64_t ldy, int32_t layout_out, double* stats, void* stream);
+
 /* Omniscient model-poisoning attacks, in place on the client matrix: rows 0 .. H-1 (H = K - byz
  * >= 2) are the honest clients, rows H .. K-1 the Byzantine ones (the reference's
  * messages[-byzantinesize:]), which are overwritten with ONE malicious row computed from the
