@@ -99,6 +99,11 @@ class GMResult:
     exchange: str = "none"   # resident runs: "agent" (flat, over XCDs), "xcd_local" (one XCD's
     #                          L2), "xcd_hier" (per-XCD gather, then the 8 XCD sums) or
     #                          "xcd_split" (one hop, own-XCD blocks from L2-kept copies)
+    # fp32 gm2 on the streaming loop (gm_delta_last_info): STEP passes run as corrections on the
+    # bf16 shadow, bit t of the mask set when STEP t was one, and "off", "armed" or "no_shadow"
+    corrections: int = 0
+    correction_mask: int = 0
+    shadow: str = "off"
 
 
 last_result: GMResult | None = None
@@ -110,12 +115,20 @@ _GUARD_NAMES = {_lib.GM_GUARD_NONE: "none", _lib.GM_GUARD_ACCEPTED: "accepted",
                 _lib.GM_GUARD_REJECTED: "rejected", _lib.GM_GUARD_ACCEPTED_FLOOR: "accepted_floor"}
 
 
-def _result(res) -> "GMResult":
-    return GMResult(res.iters, res.last_movement, bool(res.converged),
-                    _ALGO_NAMES.get(res.algo_used, "?"), _GUARD_NAMES.get(res.guard, "?"),
-                    {1: "f16_split", 2: "bf16_split", 3: "f32"}.get(res.gram_kind, ""),
-                    {1: "agent", 2: "xcd_local", 3: "xcd_hier",
-                     4: "xcd_split"}.get(res.exchange, "none"))
+def _result(res, ctx=None) -> "GMResult":
+    """ctx: the context of an fp32 gm_weiszfeld_f32 call, asked what its streaming loop did
+    with the bf16 shadow."""
+    r = GMResult(res.iters, res.last_movement, bool(res.converged),
+                 _ALGO_NAMES.get(res.algo_used, "?"), _GUARD_NAMES.get(res.guard, "?"),
+                 {1: "f16_split", 2: "bf16_split", 3: "f32"}.get(res.gram_kind, ""),
+                 {1: "agent", 2: "xcd_local", 3: "xcd_hier",
+                  4: "xcd_split"}.get(res.exchange, "none"))
+    if ctx is not None and res.algo_used == _lib.GM_ALGO_STREAM:
+        info = (C.c_int64 * 3)()
+        _lib.check(ctx.lib.gm_delta_last_info(ctx.handle, info), "gm_delta_last_info")
+        r.corrections, r.correction_mask = int(info[0]), int(info[1])
+        r.shadow = {1: "armed", 2: "no_shadow"}.get(int(info[2]), "off")
+    return r
 
 
 class Context:
@@ -386,7 +399,7 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
     context(X.device).call("gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32", X.data_ptr(), K, d,
                            ldx, g0.data_ptr(), out.data_ptr(), C.byref(o), C.byref(res),
                            _stream_ptr(X.device))
-    last_result = _result(res)
+    last_result = _result(res, None if bf16 else context(X.device))
     if pre_var is not None and not isinstance(wList, ClientPanels) and X is not wList:
         # a strided view was packed into a copy: the fused pre-noise landed in the
         # copy, and OMA's contract is in place on wList (M:351-352, as OMA() copies back)

@@ -47,6 +47,7 @@ int gm_ctx_destroy(gm_ctx* c) {
   if (c->comm) ncclCommDestroy(c->comm);
   if (c->ws) (void)hipFree(c->ws);
   if (c->stage) (void)hipFree(c->stage);
+  if (c->shadow) (void)hipFree(c->shadow);
   if (c->host) (void)hipHostFree(c->host);
   for (auto e : c->poll_ev)
     if (e) (void)hipEventDestroy(e);
@@ -329,6 +330,12 @@ static int krum_gram(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ld
   c->krum_info[1] = n;
   c->krum_info[2] = GM_KRUM_REASON_OK;
   *done = true;
+  return GM_OK;
+}
+
+int gm_delta_last_info(gm_ctx* c, int64_t* info) {
+  if (!c || !info) return fail(GM_ERR_INVALID, "gm_delta_last_info: bad args");
+  for (int i = 0; i < 3; ++i) info[i] = c->delta_info[i];
   return GM_OK;
 }
 

@@ -23,8 +23,15 @@ struct alignas(64) KState {
   double guard_r;        // last / previous K-space movement (contraction estimate)
   int32_t gram_bad;      // the reduced Gram has a non-finite entry (f16 overflow or input)
   int32_t clipped;       // centered clipping: clients with dist_k > tau at the last coefficients
-  double pad1;
+  // gm2 on panels with the bf16 shadow (KspaceArgs.delta):
+  uint32_t kind_mask;    // bit t: STEP t ran as a correction pass (t < kDeltaMaxIter)
+  uint32_t flags;        // kFlag*: what the K-space step decided for the next STEP
 };
+static_assert(sizeof(KState) == 64, "KState: one 64-byte line, as the kernels index it");
+constexpr uint32_t kFlagNextDelta = 1;     // the next STEP is a correction pass
+constexpr uint32_t kFlagWriteShadow = 2;   // the next exact STEP stores its tile as bf16
+constexpr uint32_t kFlagShadowDone = 4;    // the shadow is complete and a base pass is kept
+constexpr int kDeltaMaxIter = 32;          // correction passes only at t < 32 (the mask's bits)
 
 // Streaming pass configuration: V floats per lane per row, NW waves per
 // block, LPR lanes per row segment (chunk width J = LPR*V columns), R rows
@@ -74,6 +81,14 @@ struct PassArgs {
   // nothing, and on panels the pairing measured 1.6 % slower:
   // profiles/r6s2_rows_chunk_pair_ab.jsonl, r6s2_utcl1_rows_chunk_pair.json)
   int chunk_pair;
+  // The DELTA kernels only (kPassStepExactD / kPassStepDelta): the bf16 shadow of X in panels
+  // of the fp32 chunk's width, shadow_stride elements between its panels (written by the exact pass when
+  // kFlagWriteShadow is set, read by the correction pass through X / panel_stride), and the
+  // base iterate G (written by every exact pass, read by the correction pass).
+  uint16_t* shadow;
+  int64_t shadow_stride;
+  float* gbase;
+  int64_t slab_rows;      // slab rows the reduction sums: the larger of the two kinds' grids
 };
 
 // The first chunk of block b in a grid-stride walk (chunks b', b' + grid, ...): b itself,
@@ -116,12 +131,44 @@ struct KspaceArgs {
   int* n_done;            // problems whose tol test has fired (nullable)
   KState* mirror;         // host-mapped copy of *st written at the end (nullable, one problem)
   double tau;             // kModeCclip: the clipping radius (> 0, +inf allowed)
+  // gm2 with the bf16 shadow (mode 0 only; 0: the step as it always was).  From STEP 1 on the
+  // step reads which kind of pass just ran from st->flags, forms the distances of a correction
+  // pass as Db_k + sums[K + 2] - 2 sums[k], keeps c^b (cb) and D^b (Db) of every exact pass
+  // from STEP 1 on, and chooses the next pass's kind and whether it writes the shadow.
+  int delta;              // 1, or 2: the first exact pass that can (STEP 1) writes the shadow
+  float* cb;             // [K] the base pass's coefficients, as that pass read them
+  double* Db;             // [K] the base pass's exact squared distances
+  double theta;           // correction iff max_k |c_k - cb_k| <= theta cb_k
 };
+// theta = 2^9 eps_tile / 4: the shadow's 2^-9 relative error on sum_k |c_k - cb_k| |x_kj| then
+// stays within a quarter of the bar the exact tile is held to (eps_tile = (A + 32) 2^-24 with
+// A = R + log2(64 / LPR) + NW of the STEP tile; tests/stream_cases.py).
+inline double delta_theta(const PassCfg& cfg) {
+  int lq = 0;
+  if (cfg.LPR <= 0) return 0.0;   // no tile (the two-pass loop)
+  while ((64 / cfg.LPR) >> (lq + 1)) ++lq;
+  return (double)(cfg.R + lq + cfg.NW + 32) / (double)(1 << 17);
+}
+// The shadow is written by the pass after STEP t when the coefficients have begun to settle,
+// r_t = max_k |c_k(t+1) - c_k(t)| / c_k(t) <= kDeltaArmRatio theta, and the movement is still
+// at least kDeltaArmMove tol: the write costs 0.9 of a pass (measured at C3) and a correction
+// saves half of one, so it pays from two corrections on, and with movement contracting by up to
+// 64x per pass (C3: 60-200x) two more passes beyond the writing one run iff mv_t > 64^2 tol.
+// A wrong guess costs that 0.9 of a pass, never a bit of the result.
+constexpr double kDeltaArmRatio = 64.0;
+constexpr double kDeltaArmMove = 4096.0;
 
 // Streaming pass (stream_pass.hip).  mode: 0 step, 1 init, 2 init + ||x_k||^2, 3 Gram
 // closing sum, 4 init after OMA pre-noise written back to X (V = 4 tiles), kPassStepSelf a
 // STEP pass whose column term is the old iterate (centered clipping; PassArgs.noise = 3).
 constexpr int kPassStepSelf = 5;
+// The gm2 STEP's two kinds on fp32 panels with a bf16 shadow (DELTA = 1, 2 of the kernel
+// template): the exact pass on the fp32 tile, and the correction pass, whose cfg is a bf16
+// tile of the same chunk width and whose X / panel_stride are the shadow's.  Built for the
+// 512 < K <= 1024 tile.
+constexpr int kPassStepExactD = 6;
+constexpr int kPassStepDelta = 7;
+const void* pass_kernel_delta(const PassCfg& cfg, int mode);   // stream_pass_delta.hip
 hipError_t launch_pass(const PassCfg& cfg, int mode, int grid, const PassArgs& a, hipStream_t s,
                        int problems = 1);
 int pass_blocks_per_cu(const PassCfg& cfg, int mode);

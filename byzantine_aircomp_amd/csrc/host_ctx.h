@@ -43,6 +43,11 @@ struct gm_ctx {
   bool ws_pending = false;
   float* stage = nullptr;   // panel copy of a row-major client matrix (gm_weiszfeld_f32)
   size_t stage_bytes = 0;
+  // bf16 shadow of an fp32 panel matrix (gm2's correction passes; run_stream), kept and reused
+  // like `stage`; and what the last streaming gm2 call did with it (gm_delta_last_info)
+  uint16_t* shadow = nullptr;
+  size_t shadow_bytes = 0;
+  int64_t delta_info[3] = {0, 0, GM_DELTA_OFF};
   // A register-resident grid that failed its co-residency check-in (device_util.h
   // grid_checkin: a shared GPU, CUs held by another stream) makes the next calls stream
   // straight away instead of paying the check-in's 100 ms again; retried after this many.
@@ -289,10 +294,14 @@ struct Workspace {
   double* G;     // [KP][KP]
   double* alpha;
   double* u;
+  // gm2 with the bf16 shadow (delta): the base pass's iterate, coefficients and distances
+  float* gbase;
+  float* cb;
+  double* Db;
 };
 
 inline int ensure_ws(gm_ctx* c, int64_t K, int64_t d, int nb, Workspace* w,
-                     size_t gram_slab_n = 0, int KP = 0) {
+                     size_t gram_slab_n = 0, int KP = 0, bool delta = false) {
   const size_t S = 2 * K + 2;
   auto lay = [&](char* base) {
     Carve cv{base};
@@ -310,6 +319,9 @@ inline int ensure_ws(gm_ctx* c, int64_t K, int64_t d, int nb, Workspace* w,
     w->G = cv.take<double>((size_t)KP * KP);
     w->alpha = cv.take<double>(K);
     w->u = cv.take<double>(K);
+    w->gbase = cv.take<float>(delta ? d : 0);
+    w->cb = cv.take<float>(delta ? K : 0);
+    w->Db = cv.take<double>(delta ? K : 0);
     return cv.off;
   };
   const int rc = grow_ws(c, lay(nullptr));
@@ -409,6 +421,23 @@ inline void drop_last_timing(gm_ctx* c) {
   c->ev_used.pop_back();
 }
 
+// Gives back the timing pairs first + i with drop[i] set, of the pairs recorded from position
+// `first` on: of the two kernels gm2's shadow path queues per iteration, the one the device did
+// not choose exited at once and is no pass, like every launch queued after the stop.
+inline void drop_timings(gm_ctx* c, size_t first, const std::vector<char>& drop) {
+  if (!c->timing) return;
+  size_t keep = first;
+  for (size_t i = first; i < c->ev_used.size(); ++i) {
+    if (i - first < drop.size() && drop[i - first]) {
+      c->ev_free.push_back(c->ev_used[i].first);
+      c->ev_free.push_back(c->ev_used[i].second);
+    } else {
+      c->ev_used[keep++] = c->ev_used[i];
+    }
+  }
+  c->ev_used.resize(keep);
+}
+
 // ---- tiles -----------------------------------------------------------------------------
 
 // Streaming-pass tile for K rows.
@@ -497,6 +526,36 @@ inline bool ensure_stage(gm_ctx* c, size_t bytes) {
     return false;
   }
   c->stage_bytes = bytes;
+  return true;
+}
+
+// ---- the bf16 shadow (gm2's correction passes) -----------------------------------------
+
+// GMAGG_DELTA, read once per process: 0 never, 1 at any size, unset (or anything else) the
+// default: where 4 K d_total is at least kDeltaMinBytes.  The correction passes pay where X
+// streams from HBM: eight times the 256 MiB Infinity Cache and more.
+constexpr int64_t kDeltaMinBytes = (int64_t)1 << 31;
+inline int delta_knob() {
+  static const int v = [] {
+    const char* e = getenv("GMAGG_DELTA");
+    return !e ? -1 : e[0] == '0' && !e[1] ? 0 : e[0] == '1' && !e[1] ? 1 : -1;
+  }();
+  return v;
+}
+
+// The context's shadow buffer, at least `bytes` long; false when it cannot be had (the call
+// then runs the exact passes only).
+inline bool ensure_shadow(gm_ctx* c, size_t bytes) {
+  if (bytes <= c->shadow_bytes) return true;
+  if (c->shadow) (void)hipFree(c->shadow);   // (hipFree waits for queued work)
+  c->shadow = nullptr;
+  c->shadow_bytes = 0;
+  if (hipMalloc(&c->shadow, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->shadow = nullptr;
+    return false;
+  }
+  c->shadow_bytes = bytes;
   return true;
 }
 

@@ -338,9 +338,49 @@ int run_stream(gm_ctx* c, StreamJob& j, gm_result* res, KState* final_state = nu
   sp.mode[1] = init_mode;
   stream_grids(c, K, d, j.algo, sp.cfg[0], sp.cfg[1], init_mode, step_mode, &sp.nb[0], &sp.nb[1]);
   const int nb = std::max(sp.nb[0], sp.nb[1]);
+  // gm2 on fp32 panels: late passes as corrections on a bf16 shadow.  Whether
+  // the loop is armed follows from the job and GLOBAL sizes, so every rank of a sharded
+  // context queues the same kernels and all-reduces the same K + 3 sums.
+  PassCfg dcfg{};       // the correction pass's bf16 tile
+  int64_t Wb = 0;
+  bool delta = j.rule == Rule::Gm2 && j.panels && !j.cfg.B16 && !sp.twopass && !host_noise &&
+               noise_kind == 0 && delta_knob() != 0 &&
+               (delta_knob() == 1 || 4 * K * d_total >= kDeltaMinBytes) &&
+               pass_kernel_delta(j.cfg, kPassStepExactD) != nullptr;
+  int nb_d = 0;         // its grid
+  if (delta) {
+    // shadow panels of the fp32 chunk's width (32 columns): 4 lanes of 8 bf16 per row, 8 rows
+    // per thread, two blocks per CU
+    Wb = (int64_t)j.cfg.LPR * j.cfg.V;
+    dcfg = PassCfg{8, 8, (int)(Wb / 8), 8, 2, true};
+    delta = K <= 1024 && pass_kernel_delta(dcfg, kPassStepDelta) != nullptr;
+    nb_d = (int)std::max<int64_t>(
+        1, std::min<int64_t>((d + Wb - 1) / Wb,
+                             (int64_t)c->num_cu * pass_blocks_per_cu(dcfg, kPassStepDelta)));
+  }
+  const int64_t slab_rows = std::max(sp.nb[0], nb_d);
+  c->delta_info[0] = c->delta_info[1] = 0;
+  c->delta_info[2] = GM_DELTA_OFF;
   Workspace w;
-  int rc = ensure_ws(c, K, d, nb, &w);
+  int rc = ensure_ws(c, K, d, std::max(nb, nb_d), &w, 0, 0, delta);
   if (rc) return rc;
+  if (delta) {
+    bool have = ensure_shadow(c, sizeof(uint16_t) * (size_t)((d + Wb - 1) / Wb) * (size_t)(K * Wb));
+    if (j.tr.collective) {
+      // a rank without its buffer turns the path off on every rank: the kinds of pass, and with
+      // them what the all-reduced sums mean, must be the same everywhere
+      const double mine = have ? 0.0 : 1.0;
+      double all = 0.0;
+      HIPCHK(hipMemcpyAsync(w.sums, &mine, sizeof(double), hipMemcpyHostToDevice, s));
+      rc = allreduce(c, w.sums, 1, s);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(&all, w.sums, sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      have = all == 0.0;
+    }
+    c->delta_info[2] = have ? GM_DELTA_ARMED : GM_DELTA_NO_SHADOW;
+    delta = have;
+  }
   rc = ensure_host(c, kHostNoiseOff + sizeof(float) * (2 * K + d_total + 1) + 256);
   if (rc) return rc;
   KState* hst = host_state(c);
@@ -369,6 +409,41 @@ int run_stream(gm_ctx* c, StreamJob& j, gm_result* res, KState* final_state = nu
   ka.n_last = w.hnoise + d;
   ka.coef = w.coef;
   ka.st = w.st;
+  ka.delta = !delta ? 0 : delta_knob() == 1 ? 2 : 1;   // 2: the shadow is written in STEP 1
+  ka.cb = w.cb;
+  ka.Db = w.Db;
+  ka.theta = delta ? delta_theta(j.cfg) : 0.0;   // (the two-pass loop has no tile: cfg is unset)
+  const size_t timing_first = c->ev_used.size();
+
+  // STEP t >= 1 of an armed loop: the exact pass and the correction pass are both queued, the
+  // K-space step of t - 1 has chosen one and the other exits at once; each runs on its own grid,
+  // writes slab rows of K + 3 sums and zeroes the rows only the other's larger grid would fill.
+  auto delta_pair = [&](int64_t t) -> int {
+    PassArgs a = sp.a;
+    a.g_old = w.g[(t - 1) & 1];
+    a.g_new = w.g[t & 1];
+    a.slab_stride = K + 3;
+    a.iter = t;
+    a.shadow = c->shadow;
+    a.shadow_stride = K * Wb;
+    a.gbase = w.gbase;
+    a.slab_rows = slab_rows;
+    PassArgs b = a;
+    b.X = reinterpret_cast<const float*>(c->shadow);
+    b.ldx = b.panel_stride = K * Wb;
+    const PassArgs* args[2] = {&a, &b};
+    for (int kind = 0; kind < 2; ++kind) {
+      hipEvent_t e0, e1;
+      int rc2 = record_pass_begin(c, s, &e0, &e1);
+      if (rc2) return rc2;
+      HIPCHK(launch_pass(kind ? dcfg : j.cfg, kind ? kPassStepDelta : kPassStepExactD,
+                         kind ? nb_d : sp.nb[0], *args[kind], s));
+      rc2 = record_pass_end(c, s, e0, e1);
+      if (rc2) return rc2;
+    }
+    HIPCHK(launch_slab_reduce(w.slab, (int)slab_rows, K + 3, w.sums, w.st, s));
+    return allreduce(c, w.sums, K + 3, s);
+  };
 
   auto poll = [&](KState* dst) -> int {
     HIPCHK(hipMemcpyAsync(dst, w.st, sizeof(KState), hipMemcpyDeviceToHost, s));
@@ -378,6 +453,7 @@ int run_stream(gm_ctx* c, StreamJob& j, gm_result* res, KState* final_state = nu
 
   // Pass over X: INIT (t = -1) or STEP t; leaves the reduced partials in w.sums.
   auto do_pass = [&](int64_t t) -> int {
+    if (delta && t >= 1) return delta_pair(t);
     const int rc2 = t <= 0 ? stream_pass(sp, t, j.guess0, 0, t < 0 ? nullptr : w.g[0])
                            : stream_pass(sp, t, w.g[(t - 1) & 1], 0, w.g[t & 1]);
     return rc2 ? rc2 : allreduce(c, w.sums, t < 0 ? 2 * K + 2 : K + 2, s);
@@ -464,7 +540,22 @@ int run_stream(gm_ctx* c, StreamJob& j, gm_result* res, KState* final_state = nu
   r.guard = j.guard_rejected ? GM_GUARD_REJECTED : GM_GUARD_NONE;
   if (r.iters < 1) return fail(GM_ERR_HIP, "Weiszfeld loop recorded no iteration");
   // passes queued after the stop (lagged poll) exited at once: not timed as passes
-  for (int64_t k = r.iters; k < enqueued; ++k) drop_last_timing(c);
+  if (!delta) {
+    for (int64_t k = r.iters; k < enqueued; ++k) drop_last_timing(c);
+  } else {
+    // one record for STEP 0, then (exact, correction) per iteration: keep the kind that ran
+    const uint32_t mask = final_st->kind_mask;
+    std::vector<char> drop(1 + 2 * (size_t)std::max<int64_t>(0, enqueued - 1), 0);
+    for (int64_t k = 1; k < enqueued; ++k) {
+      const bool ran = k < r.iters;
+      const bool corr = k < kDeltaMaxIter && ((mask >> k) & 1u) != 0;
+      drop[1 + 2 * (k - 1)] = !ran || corr;
+      drop[2 + 2 * (k - 1)] = !ran || !corr;
+    }
+    drop_timings(c, timing_first, drop);
+    c->delta_info[0] = __builtin_popcount(mask);
+    c->delta_info[1] = mask;
+  }
   HIPCHK(hipMemcpyAsync(j.out, w.g[(r.iters - 1) & 1], sizeof(float) * d, hipMemcpyDeviceToDevice,
                         s));
   if (res) *res = r;

@@ -91,6 +91,8 @@ static const void* pass_fn_mode(int mode, bool panel) {
 }
 
 static const void* pass_kernel(const PassCfg& cfg, int mode, bool panel = false) {
+  if (mode == kPassStepExactD || mode == kPassStepDelta)   // stream_pass_delta.hip
+    return panel ? pass_kernel_delta(cfg, mode) : nullptr;
   if (cfg.B16) return pass_kernel_bf16(cfg, mode, panel);
   if (mode == kPassStepSelf) return pass_kernel_self(cfg, panel);   // stream_pass_cclip.hip
 #define GMK_CASE(V_, W_, L_, R_, O_)                                                 \
@@ -119,7 +121,7 @@ hipError_t launch_pass(const PassCfg& cfg, int mode, int grid, const PassArgs& a
 }
 
 int pass_blocks_per_cu(const PassCfg& cfg, int mode) {
-  const void* fn = pass_kernel(cfg, mode);
+  const void* fn = pass_kernel(cfg, mode, mode == kPassStepExactD || mode == kPassStepDelta);
   int n = 0;
   if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, cfg.NW * 64, 0) != hipSuccess ||
       n < 1)

@@ -63,4 +63,16 @@ const void* pass_kernel_bf16(const PassCfg& cfg, int mode, bool panel) {
   return nullptr;
 }
 
+// The correction pass of gm2 on a bf16 shadow of fp32 panels (DELTA = 2; stream_pass_delta.hip
+// dispatches).  The shadow's panels are as wide as the fp32 chunk that writes them (32 columns at
+// 512 < K <= 1024), so the tile is 1024 rows x 32 columns: 4 lanes per 64-byte row, 8 rows per
+// thread, 64 KiB per chunk, on the plain schedule, two blocks per CU (87 VGPRs, no scratch).
+// Three blocks per CU (80 VGPRs, 28 bytes of scratch) measured slower at C3: 3.48 against
+// 3.28 ms per pass, three interleaved rounds.
+const void* pass_kernel_bf16_delta(const PassCfg& cfg) {
+  if (!(cfg.B16 && cfg.V == 8 && cfg.NW == 8 && cfg.LPR == 4 && cfg.R == 8 && cfg.OCC == 2))
+    return nullptr;
+  return reinterpret_cast<const void*>(&weiszfeld_pass<8, 8, 4, 8, 0, 0, 2, true, true, false, 2>);
+}
+
 }  // namespace gmk

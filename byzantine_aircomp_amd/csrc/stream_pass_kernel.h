@@ -23,8 +23,12 @@ namespace gmk {
 // low half is the even column), and an element is widened where it is used (xpair): exact,
 // bf16 -> fp32 is `bits << 16`.  Expanded to fp32 the tile would take twice the registers
 // and lose the occupancy the K <= 1024 tile's rate depends on.
-template <int V, int R, bool B16 = false>
-struct Tile {
+// GB: the tile also carries the base iterate G at the finisher thread's column (the
+// correction pass, DELTA = 2).  A base class, so that every other tile is the struct it was.
+template <bool GB> struct TileBase {};
+template <> struct TileBase<true> { float gb; };
+template <int V, int R, bool B16 = false, bool GB = false>
+struct Tile : TileBase<GB> {
   static_assert(!B16 || V == 8, "bf16 tiles: 8 columns = one 16-byte load per lane");
   typedef typename std::conditional<B16, uint32_t, float>::type word;
   word x[R][B16 ? V / 2 : V];
@@ -49,10 +53,24 @@ struct Tile {
 // (centered clipping; a.noise is 3 and no draw is added), with phase A's sums in fp64 (see
 // there).  A template parameter, not a fourth runtime kind: gm2 / gm are to run the code
 // they ran before.
+// DELTA (gm2 STEP on panels, from the second STEP on): the two kernels of an
+// iteration whose kind the K-space step has chosen (KState.flags); the one not chosen exits.
+//   1  the exact fp32 pass.  It also writes its iterate to a.gbase (the base G of later
+//      corrections) and, where kFlagWriteShadow is set, stores the tile it holds as bf16 (the
+//      bits of pack.hip's rounding) into a.shadow: bf16 panels of the fp32 chunk's own width,
+//      fp32 chunk ch = shadow panel ch.
+//   2  the correction pass on the bf16 shadow (B16, PANEL).  a.coef holds c_k - c^b_k; phase A
+//      is g' = G + sum_k (c_k - c^b_k) x~_k, phase B the row sums e_k = sum_j D_j x~_kj with
+//      D = g' - G, and the finisher threads sum C = sum_j D_j (D_j + 2 G_j) into a third slab
+//      value: ||x~_k - g'||^2 - ||x~_k - G||^2 = C - 2 e_k, which the K-space step adds to the
+//      base pass's exact distances.
 template <int V, int NW, int LPR, int R, int MODE, int SCHED, int OCC = 1, bool PANEL = false,
-          bool B16 = false, bool SELF = false>
+          bool B16 = false, bool SELF = false, int DELTA = 0>
 __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs a) {
   static_assert(!SELF || MODE == 0, "the old iterate as column term: STEP passes only");
+  static_assert(DELTA == 0 || (MODE == 0 && PANEL && !SELF), "DELTA: gm2 STEP on panels");
+  static_assert(DELTA != 1 || (!B16 && V == 4), "the shadow is written from the fp32 tile");
+  static_assert(DELTA != 2 || (B16 && SCHED == 0), "the correction pass reads the bf16 shadow");
   constexpr bool PIPE = SCHED == 1, ROLL = SCHED == 2 || SCHED == 3, ROLL2 = SCHED == 3;
   constexpr bool SUM_ONLY = MODE == 3;     // closing pass of the Gram variant: g = sum c_k x_k
   constexpr bool OMA_INIT = MODE == 4;
@@ -66,12 +84,13 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
   constexpr int J = LPR * V;
   constexpr int RPL = R > LPR ? R / LPR : 1;
   static_assert(J <= NW * 64, "one finisher thread per column");
-  using T = Tile<V, R, B16>;
+  using T = Tile<V, R, B16, DELTA == 2>;
+  constexpr int NFIN = DELTA == 2 ? 3 : 2;
 
   typedef typename std::conditional<SELF, double, float>::type red_t;   // SELF: phase A in fp64
   __shared__ red_t s_red[NW][J];
   __shared__ float s_g[INIT ? 2 : 1][J];   // INIT: by chunk parity (one barrier per chunk)
-  __shared__ double s_fin[2][NW];
+  __shared__ double s_fin[NFIN][NW];
   __shared__ float s_w[OCC > 1 ? NW * QW * R : 1];
 
   if (gridDim.y > 1) {                       // batched independent problems
@@ -86,6 +105,13 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
     a.oma_seed += (uint64_t)pb * kSeedStride;
   }
   if (!SUM_ONLY && a.st->done) return;
+  bool wr_shadow = false;
+  (void)wr_shadow;
+  if constexpr (DELTA != 0) {
+    const uint32_t fl = a.st->flags;
+    if (((fl & kFlagNextDelta) != 0) != (DELTA == 2)) return;
+    wr_shadow = DELTA == 1 && (fl & kFlagWriteShadow) != 0;
+  }
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -196,6 +222,7 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
     const bool fin = tid < J && ch < nch && gj < d;
     t.gold = fin ? a.g_old[gj] : 0.f;
     if constexpr (!INIT) t.hn = (fin && a.noise == 2) ? a.hnoise[gj] : 0.f;
+    if constexpr (DELTA == 2) t.gb = fin ? a.gbase[gj] : 0.f;
   };
   auto fetch = [&](int64_t ch, T& t) {
 #pragma unroll
@@ -206,7 +233,7 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
   double row_acc[RPL], row_acc2[RPL];
 #pragma unroll
   for (int m = 0; m < RPL; ++m) row_acc[m] = row_acc2[m] = 0.0;
-  double mv_acc = 0.0, gn_acc = 0.0;
+  double mv_acc = 0.0, gn_acc = 0.0, cg_acc = 0.0;
 
   // ROLL: row i of chunk `nxt` is loaded into t.x[i] as soon as phase B has
   // consumed row i of chunk ch, so the next chunk's loads are in flight during
@@ -244,9 +271,41 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
       }
     }
   };
+  // DELTA = 1: the fp32 tile of chunk ch, rounded to bf16 (to nearest even, NaN -> 0x7FC0: the
+  // bits pack.hip produces), into shadow panel ch, a panel of the fp32 chunk's own width: 8 bytes
+  // per lane and row, rows J * 2 bytes apart, so a wave instruction writes QW whole adjacent
+  // rows and a block one contiguous K * J * 2 bytes.  (Two fp32 chunks per 64-column bf16 panel,
+  // 64-byte halves of 128-byte rows written by different blocks at different times, made the
+  // writing pass 16.0 ms against 6.3 ms for the plain pass at C3: DESIGN.md §3.1.)  Padding
+  // columns are 0 in the tile and are stored as 0; rows >= K are not stored (the buffer holds
+  // ceil(d / J) whole panels of K rows).
+  auto store_shadow = [&](int64_t ch, const auto& t) {
+    auto rne = [](float f) -> uint32_t {
+      const uint32_t u = __float_as_uint(f);
+      return f != f ? 0x7fc0u : (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    };
+    // as the loads: one buffer resource per row group in SGPRs, sized to the rows that exist
+    // (a store to a row >= K is dropped by the range check), + one lane offset
+    constexpr int RB = J * 2;                         // bytes per row of a shadow panel
+    char* const pan = reinterpret_cast<char*>(a.shadow + ch * a.shadow_stride);
+    const uint32_t vo = (uint32_t)(q * RB + c * V * 2);
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int64_t wb = (int64_t)(w * QW + NRG * i) * RB;
+      const int64_t nrec = (int64_t)K * RB - wb;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          pan + wb, 0, nrec <= 0 ? 0 : (int)nrec, 0x00020000);
+      typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+      const u2 o = u2{rne(t.x[i][0]) | rne(t.x[i][1]) << 16, rne(t.x[i][2]) | rne(t.x[i][3]) << 16};
+      __builtin_amdgcn_raw_buffer_store_b64(o, rs, vo, 0, 0);
+    }
+  };
   auto process = [&](int64_t ch, T& t, int64_t nxt) {
     float gv[V];
     zero_padding(ch, t);
+    if constexpr (DELTA == 1) {
+      if (wr_shadow) store_shadow(ch, t);
+    }
     if constexpr (OMA_INIT) oma_tile(ch, t);
     if constexpr (INIT) {
       // the guess at this chunk's columns -> LDS (buffer by parity: a thread still
@@ -336,10 +395,18 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
           }
           // centered clipping: the old iterate's share a = 1 - sum_k c_k (already here as gold)
           if constexpr (SELF) gnew = (float)fma((double)a_noise, (double)t.gold, (double)sum);
+          if constexpr (DELTA == 2) gnew = t.gb + sum;
           a.g_new[gj] = gnew;
+          if constexpr (DELTA == 1) a.gbase[gj] = gnew;
           const float diff = t.gold - gnew;
           mv_acc += (double)(diff * diff);
           gn_acc += (double)(gnew * gnew);
+        }
+        if constexpr (DELTA == 2) {
+          // phase B's column operand is the displacement of the STORED iterate from the base
+          const float dj = gj < d ? gnew - t.gb : 0.f;
+          cg_acc += (double)dj * ((double)dj + 2.0 * (double)t.gb);
+          gnew = dj;
         }
         s_g[0][tid] = gnew;
       }
@@ -372,6 +439,10 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
 #pragma unroll
         for (int j = 0; j < V / 2; ++j) {
           const f2 xv = xpair(t, i, j);
+          if constexpr (DELTA == 2) {
+            sp = __builtin_elementwise_fma(xv, f2{gv[2 * j], gv[2 * j + 1]}, sp);
+            continue;
+          }
           const f2 tt = xv - f2{gv[2 * j], gv[2 * j + 1]};
           sp = __builtin_elementwise_fma(tt, tt, sp);
           if constexpr (WANT_R) sp2 = __builtin_elementwise_fma(xv, xv, sp2);
@@ -458,10 +529,20 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
       }
     }
   }
+  if constexpr (DELTA != 0) {
+    // the two kinds run on grids of their own and one slab_reduce sums a.slab_rows rows: the
+    // rows only the other kind's larger grid would fill are zeros
+    for (int64_t r = blockIdx.x + grid; r < a.slab_rows; r += grid)
+      for (int64_t k2 = tid; k2 < a.slab_stride; k2 += NW * 64) a.slab[r * a.slab_stride + k2] = 0.0;
+  }
   const double mv = wave_sum(mv_acc), gn = wave_sum(gn_acc);
   if (lane == 0) {
     s_fin[0][w] = mv;
     s_fin[1][w] = gn;
+  }
+  if constexpr (DELTA == 2) {
+    const double cg = wave_sum(cg_acc);
+    if (lane == 0) s_fin[2][w] = cg;
   }
   __syncthreads();
   if (tid == 0) {
@@ -474,6 +555,12 @@ __global__ void __launch_bounds__(NW * 64, OCC * NW / 4) weiszfeld_pass(PassArgs
     const int64_t b = SUM_ONLY ? 0 : INIT ? 2 * K : K;
     out[b] = m;
     out[b + 1] = g;
+    if constexpr (DELTA == 2) {
+      double cg = 0.0;
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) cg += s_fin[2][ww];
+      out[b + 2] = cg;
+    }
   }
 }
 

@@ -60,6 +60,68 @@ __global__ void __launch_bounds__(1024) slab_reduce(const double* __restrict__ s
 // next pass's coefficients.  One block.
 __device__ void kspace_body(KspaceArgs& a);
 
+// gm2's coefficients when late STEP passes may run as corrections on the bf16 shadow of X
+// (KspaceArgs.delta).  The pass that just ran (t) was
+//   a correction (ran_delta): its sums are e_k = sum_j D_j x~_kj and C = sum_j D_j (D_j + 2 G_j)
+//     with D = g' - G, and the distances are D^b_k + C - 2 e_k on the base pass's exact D^b;
+//   exact: the sums are the distances; from STEP 1 on that pass also wrote the base iterate, so
+//     it becomes the base: c^b = the coefficients it read, D^b = its distances.  If it was asked
+//     to, it has also written the shadow, which is complete from then on.
+// The next pass is a correction iff the shadow is complete, t + 1 < kDeltaMaxIter and
+// |c_k - c^b_k| <= theta c^b_k for every k (false on NaN); a.coef then holds c_k - c^b_k (exact:
+// the two fp32 values are within a factor of two), else c_k.  While there is no shadow, the next
+// exact pass is asked to write it by the rule at kDeltaArmRatio (gmagg_internal.h).
+__device__ void kspace_gm2_delta(KspaceArgs& a, bool ran_delta, uint32_t fl_in, double* scratch) {
+  KState* st = a.st;
+  const int tid = threadIdx.x;
+  const int64_t K = a.K;
+  const bool init = a.t < 0;
+  const bool new_base = !ran_delta && a.t >= 1;
+  const bool shadow_done = (fl_in & kFlagShadowDone) != 0 ||
+                           (new_base && (fl_in & kFlagWriteShadow) != 0);
+  const double C = ran_delta ? a.sums[K + 2] : 0.0;
+  auto dist2 = [&](int64_t k) {
+    return ran_delta ? fmax(a.Db[k] + C - 2.0 * a.sums[k], 0.0) : a.sums[k];
+  };
+  double wsum = 0.0;
+  for (int64_t k = tid; k < K; k += blockDim.x) wsum += 1.0 / (double)clamp_dist(dist2(k), a.eps);
+  const double W = block_sum(wsum, scratch);
+  // c^b for the guard, the previous pass's c for the arming rule (the same thread reads and
+  // later writes element k of every array: no barrier between)
+  double viol = 0.0, unsettled = 0.0;
+  for (int64_t k = tid; k < K; k += blockDim.x) {
+    const double ck = (double)(float)((1.0 / (double)clamp_dist(dist2(k), a.eps)) / W);
+    if (shadow_done) {
+      const double cbk = new_base ? (double)a.coef[k] : (double)a.cb[k];
+      if (!(fabs(ck - cbk) <= a.theta * cbk)) viol += 1.0;
+    } else if (!init) {
+      const double cp = (double)a.coef[k];
+      if (!(fabs(ck - cp) <= kDeltaArmRatio * a.theta * cp)) unsettled += 1.0;
+    }
+  }
+  const double nviol = block_sum(viol, scratch);
+  const double nuns = block_sum(unsettled, scratch);
+  const bool next_delta = shadow_done && nviol == 0.0 && a.t + 1 < kDeltaMaxIter;
+  for (int64_t k = tid; k < K; k += blockDim.x) {
+    const float ck = (float)((1.0 / (double)clamp_dist(dist2(k), a.eps)) / W);
+    if (new_base) {
+      a.cb[k] = a.coef[k];
+      a.Db[k] = a.sums[k];
+    }
+    a.coef[k] = next_delta ? (float)((double)ck - (double)a.cb[k]) : ck;
+  }
+  if (tid == 0) {
+    const float mv = init ? 0.f : (float)sqrt(a.sums[K]);
+    // (delta == 2, GMAGG_DELTA=1: the rule weighs cost, as the size threshold does, and is
+    // bypassed with it; the guard on theta never is)
+    const bool arm = !init && !shadow_done && a.t + 2 < kDeltaMaxIter &&
+                     (a.delta == 2 ||
+                      (nuns == 0.0 && (double)mv > kDeltaArmMove * (double)a.tol));
+    st->flags = (shadow_done ? kFlagShadowDone : 0u) | (next_delta ? kFlagNextDelta : 0u) |
+                (arm ? kFlagWriteShadow : 0u);
+  }
+}
+
 // With a.mirror set, thread 0 copies the final KState into host-mapped memory as the
 // kernel's last act (plain vector stores; visible to the host once an event recorded
 // after this kernel has completed): the lagged convergence poll reads it there instead of
@@ -90,9 +152,15 @@ __device__ void kspace_body(KspaceArgs& a) {
   const bool init = a.t < 0;
   const double* D2 = a.sums;
   const double gn2 = init ? a.sums[2 * K + 1] : a.sums[K + 1];
+  // gm2 with the bf16 shadow: the kind of the pass that just ran, as the previous step chose
+  // it (every thread reads the flags here; thread 0 rewrites them only behind the barriers of
+  // kspace_gm2_delta's sums).  STEP 0 is always the plain exact pass.
+  const uint32_t fl_in = a.delta ? st->flags : 0u;
+  const bool ran_delta = a.delta && a.t >= 1 && (fl_in & kFlagNextDelta) != 0;
 
   if (tid == 0) {
     s_stop = 0;
+    if (ran_delta) st->kind_mask |= 1u << a.t;
     if (a.do_check && !init) {
       const float mv = (float)sqrt(a.sums[K]);   // (guess - guess_next).norm() (M:180)
       st->last_movement = (double)mv;
@@ -110,6 +178,10 @@ __device__ void kspace_body(KspaceArgs& a) {
   __syncthreads();
   if (s_stop || !a.do_coef) return;
 
+  if (a.mode == 0 && a.delta) {
+    kspace_gm2_delta(a, ran_delta, fl_in, scratch);
+    return;
+  }
   if (a.mode == 0) {
     // gm2: g' = sum_k x_k/d_k / sum_k 1/d_k  (M:179), weights normalised here.
     double wsum = 0.0;

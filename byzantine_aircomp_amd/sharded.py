@@ -167,7 +167,7 @@ class ShardedGM:
         res = _lib.GmResult()
         self.ctx.call("gm_weiszfeld_f32", ptr, X.shape[0], self.d_local, ldx, g0.data_ptr(),
                       out.data_ptr(), C.byref(o), C.byref(res), _stream_ptr(self.device))
-        self.last_result = _result(res)
+        self.last_result = _result(res, self.ctx)
         if o.pre_oma and X is not X_in:
             X_in.copy_(X)      # the fused pre-noise is in place on the caller's shard
         return out

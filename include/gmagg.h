@@ -190,6 +190,28 @@ int gm_weiszfeld_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t 
                      const float* guess0, float* out, const gm_opts* opts,
                      gm_result* result, void* stream);
 
+/* gm2 on fp32 panels at 512 < K <= 1024 (the streaming path): once the Weiszfeld coefficients
+ * have settled, a STEP pass may run as a CORRECTION on a bf16 copy of X (the shadow) that the
+ * context owns: 2 K d more bytes of device memory, written by one of the exact passes; X itself
+ * is never written.  With the most recent exact pass as base (coefficients c^b, output G, exact
+ * distances D^b), g' = G + sum_k (c_k - c^b_k) bf16(x_k) and the distances follow in the same
+ * read, so the pass moves half the bytes.  It runs only while |c_k - c^b_k| <= theta c^b_k for
+ * every k (decided on the device from the all-reduced sums, the same on every rank of a
+ * sharded context), theta = 2^9 eps / 4 with eps the tile's per-element bound (59 * 2^-24), so
+ * the result agrees with the exact passes' to a quarter of that bound; otherwise the pass is
+ * exact, as every pass is when the shadow cannot be allocated.
+ * GMAGG_DELTA (environment, read once per process): 0 never; 1 at any size, the shadow written
+ * by the second STEP whatever the cost rule says; by default the path is taken where
+ * 4 K d_total >= 2 GiB and the shadow is written once the coefficients have begun to settle.
+ * gm_delta_last_info: info[3] = {correction passes, bit t set when STEP t was one (t < 32),
+ * gm_delta_status} of this context's last gm_weiszfeld_f32 call that ran the streaming loop. */
+enum gm_delta_status {
+  GM_DELTA_OFF = 0,          /* not eligible, below the size threshold or turned off */
+  GM_DELTA_ARMED = 1,        /* the loop could take correction passes (info[0] says how many) */
+  GM_DELTA_NO_SHADOW = 2     /* eligible, but the shadow could not be allocated: exact passes */
+};
+int gm_delta_last_info(gm_ctx* ctx, int64_t* info);
+
 /* Panel width W of the GM_LAYOUT_PANELS layout for K clients (the streaming
  * tile's chunk width: 32 columns at 512 < K <= 1024); 0 if K is unsupported. */
 int64_t gm_panel_width(int64_t K);
