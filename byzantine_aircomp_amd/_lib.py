@@ -154,6 +154,9 @@ SIGNATURES = [
     ("gm_client_chain_f32", C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64,
                                       C.c_int32, C.c_float, C.c_float, _P, _P, _P, _I64,
                                       C.c_int32, _P]),
+    ("gm_client_grads_f32", C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64,
+                                      C.c_int32, C.c_float, C.c_float, _P, _P, _P, _I64,
+                                      C.c_int32, _P]),
     ("gm_fill_clients_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_uint64, _P]),
     ("gm_fill_normal_f32", C.c_int, [_P, _P, _I64, C.c_float, C.c_float, C.c_uint64, _P]),

@@ -892,6 +892,40 @@ int gm_client_chain_f32(gm_ctx* c, const float* data, int64_t ldd, const int64_t
   return GM_OK;
 }
 
+int gm_client_grads_f32(gm_ctx* c, const float* data, int64_t ldd, const int64_t* labels,
+                        int64_t F, int64_t C, const int32_t* idx, int64_t K, int64_t B,
+                        int64_t honest, int32_t attack, float beta, float weight_decay,
+                        const float* W, const float* b, float* M, int64_t ldx, int32_t layout,
+                        void* stream) {
+  if (!c || !data || !labels || !idx || !W || !b || !M || K < 1 || K > INT32_MAX || B < 1 ||
+      F < 1 || C < 1 || honest < 0 || honest > K || ldd < F || attack < 0 || attack > 2 ||
+      (layout != GM_LAYOUT_ROWS && layout != GM_LAYOUT_PANELS) || !(beta >= 0.f && beta < 1.f))
+    return fail(GM_ERR_INVALID, "gm_client_grads_f32: bad args");
+  if (!client_grads_supported(F, C, B))
+    return fail(GM_ERR_UNSUPPORTED, "gm_client_grads_f32: needs F <= 832, C <= 64, B <= 64 "
+                "(F=%lld C=%lld B=%lld)", (long long)F, (long long)C, (long long)B);
+  const int64_t d = C * F + C;
+  ClientGradArgs a{};
+  a.data = data; a.ldd = ldd; a.labels = labels; a.F = F; a.C = C; a.idx = idx;
+  a.K = K; a.B = B; a.honest = honest; a.attack = attack; a.beta = beta; a.wd = weight_decay;
+  a.W = W; a.b = b; a.M = M;
+  if (layout == GM_LAYOUT_PANELS) {
+    const int64_t Wp = gm_panel_width(K);
+    if (Wp == 0)
+      return fail(GM_ERR_UNSUPPORTED, "gm_client_grads_f32: K=%lld has no panel width",
+                  (long long)K);
+    if (ldx < K * Wp) return fail(GM_ERR_INVALID, "gm_client_grads_f32: panel stride");
+    a.pstride = ldx;
+    a.wshift = wshift_of(Wp);
+  } else {
+    if (ldx < d) return fail(GM_ERR_INVALID, "gm_client_grads_f32: ldx < C*F + C");
+    a.ldx = ldx;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(launch_client_grads(a, reinterpret_cast<hipStream_t>(stream)));
+  return GM_OK;
+}
+
 int gm_oma_apply_f32(gm_ctx* c, float* X, int64_t K, int64_t d, int64_t ldx, const float* hr,
                      const float* hi, const float* nr, const float* ni, void* stream) {
   if (!c || !X || !hr || !hi || !nr || !ni || K < 0 || d < 0 || ldx < d)

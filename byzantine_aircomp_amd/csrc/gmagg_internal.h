@@ -408,6 +408,28 @@ struct ClientChainArgs {
 bool client_chain_supported(int64_t F, int64_t C, int64_t B);
 hipError_t launch_client_chain(const ClientChainArgs& a, hipStream_t s);
 
+// The clients' gradients at one model, folded into their momenta (client_grads.hip): one
+// workgroup per client.
+struct ClientGradArgs {
+  const float* data;      // training set [n][ldd] fp32 (row = one flattened sample)
+  int64_t ldd;
+  const int64_t* labels;  // [n]
+  int64_t F, C;           // features, classes (the MLP's weight is [C][F])
+  const int* idx;         // [K][B] dataset rows of each client's batch
+  int64_t K, B, honest;
+  int attack;             // 0 none, 1 classflip, 2 dataflip
+  float beta, wd;
+  const float* W;         // [C][F], read only
+  const float* b;         // [C], read only
+  float* M;               // momentum matrix: rows [K][ldx] or panels, updated in place
+  int64_t ldx;            // rows: row stride
+  int64_t pstride;        // > 0: panels, elements between panels (panel width 1 << wshift)
+  int wshift;
+  int stage;              // (set by launch_client_grads) the batch tile staged in LDS
+};
+bool client_grads_supported(int64_t F, int64_t C, int64_t B);
+hipError_t launch_client_grads(const ClientGradArgs& a, hipStream_t s);
+
 // OMA / synthetic fills (oma.hip).
 hipError_t launch_oma_apply(float* X, int64_t K, int64_t d, int64_t ldx, const float* hr,
                             const float* hi, const float* nr, const float* ni, hipStream_t s);

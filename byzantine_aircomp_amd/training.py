@@ -14,6 +14,11 @@ from per-client `.cpu()` copies (M:304, M:341) stacked by `flatten_list`
   * `SGD` (row f4): the same signature, schedule, attacks, RNG consumption and
     outputs as the reference loop, calling any aggregator with the reference's
     `aggregate(wList, options)` contract (ours: `gm2`, `gm`, ...).
+  * `MomentumSGD`: the worker-momentum loop in gradient space (Karimireddy, He & Jaggi,
+    ICML 2021, Algorithm 1; "robust D-SHB"), the loop cclip, NNM, DnC, FLTrust, ARC and
+    the omniscient attacks are defined on: every client's gradient at the SAME model,
+    folded into its momentum by one HIP kernel (gm_client_grads_f32), the momenta
+    aggregated, the model stepped.  Not the reference's; SGD stays what the reference runs.
   * `run` / `modelFactory` / `calculateAccuracy` / `getVarience`: the driver
     pieces needed to produce records with the reference's keys and titles, so
     draw.ipynb-style plots read them unchanged.
@@ -41,7 +46,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-__all__ = ["ClientUpdates", "SGD", "run", "modelFactory", "MLP", "setup_seed",
+__all__ = ["ClientUpdates", "SGD", "MomentumSGD", "run", "modelFactory", "MLP", "setup_seed",
            "calculateAccuracy", "getVarience", "classflip", "dataflip", "weightflip",
            "ATTACK_NAMES", "attack_by_name"]
 
@@ -301,6 +306,31 @@ class _ClientChain:
                 float(wd), Wt.data_ptr(), bt.data_ptr(), buf.data_ptr(), ldx, lay,
                 _stream_ptr(self.device)), "gm_client_chain_f32")
 
+    def grads(self, local, M, honest, attack_name, beta, wd):
+        """M_k <- beta M_k + (1 - beta) (grad meanCE(theta; batch k) + wd theta) for every
+        client at the model's current theta, in place on M (a [K, d] tensor or ClientPanels):
+        one launch of gm_client_grads_f32 (client_grads.hip), one workgroup per client."""
+        from . import _lib
+        from .aggregators import _stream_ptr
+        from .panels import ClientPanels
+        K = local.shape[0] if local.dim() == 2 else -1
+        if local.shape != (K, self.B):
+            raise RuntimeError("client batches must be full batches of batchSize samples")
+        idx = (local + self.cuts).to(self.device, non_blocking=True)
+        Wt, bt = self.lin.weight, self.lin.bias
+        if not (Wt.is_contiguous() and bt.is_contiguous()):
+            raise RuntimeError("the model's weight and bias must be contiguous")
+        if isinstance(M, ClientPanels):
+            buf, ldx, lay = M.data, M.panel_stride, _lib.GM_LAYOUT_PANELS
+        else:
+            buf, ldx, lay = M, M.stride(0), _lib.GM_LAYOUT_ROWS
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gm_client_grads_f32(
+                self.ctx.handle, self.x.data_ptr(), self.F, self.y.data_ptr(), self.F, self.C,
+                idx.data_ptr(), K, self.B, honest, self.ATTACK.get(attack_name, 0), float(beta),
+                float(wd), Wt.data_ptr(), bt.data_ptr(), buf.data_ptr(), ldx, lay,
+                _stream_ptr(self.device)), "gm_client_grads_f32")
+
 
 # ---- the federated loop (row f4) ---------------------------------------------------
 
@@ -408,6 +438,148 @@ def SGD(model, gamma, aggregate, weight_decay, noise_var=None, honestSize=0,  # 
                     OMA(X, noise_var)                     # M:351-352
             clients.load(aggregate(X, options))           # M:353-358
         paths["var"].append(getVarience(clients.X, honestSize).cpu())
+        tl, ta = train_eval()
+        vl, va = calculateAccuracy(model, loss_func, val_all, device)
+        for key, v in (("train_loss", tl), ("train_acc", ta), ("val_loss", vl), ("val_acc", va)):
+            paths[key].append(v)
+        if verbose:
+            _log(f"[{r + 1}/{rounds}] train: loss={tl:.4f} acc={ta:.4f} "
+                 f"val: loss={vl:.4f} acc={va:.4f}")
+    return (model, paths["train_loss"], paths["train_acc"], paths["val_loss"], paths["val_acc"],
+            paths["var"])
+
+
+def MomentumSGD(model, gamma, aggregate, weight_decay, noise_var=None, honestSize=0,  # noqa: N802
+                byzantineSize=0, attack=None, rounds=10, displayInterval=1000, SEED=None,
+                fixSeed=False, loss_func=None, train_dataset=None, validate_dataset=None,
+                device=None, batchSize=None, num_classes=10, verbose=True, layout="rows",
+                eval_train=True, client_kernel="auto", beta=0.9, **kw):
+    """Robust distributed SGD with worker momentum, in gradient space (Karimireddy, He &
+    Jaggi, ICML 2021, Algorithm 1; Farhadkhani et al., ICML 2022, "robust D-SHB"): SGD's
+    signature, shards, samplers, RNG consumption, records and return tuple, plus `beta`.
+    Per step, at the model theta every client shares:
+
+        g_k = grad meanCE(theta; batch k) + weight_decay * theta
+        m_k <- beta * m_k + (1 - beta) * g_k             (m_k = 0 before the first step)
+        R = aggregate(M, options);  theta <- theta - gamma * R
+
+    client_kernel: as SGD's; with the kernel the K momentum updates are ONE launch of
+    gm_client_grads_f32 (one workgroup per client) on M, a [K, d] tensor or ClientPanels as
+    `layout` says; without it a per-client torch autograd loop at the same theta applies the
+    same formula (also the CPU path).
+    attack: classflip / dataflip act on the Byzantine clients' batches; any other attack is
+    called as attack(M, byzantineSize) and overwrites the last rows of M in place.
+    options["guess"] is the previous step's aggregate; None on the first step, so each
+    aggregator takes its own default (the column mean for gm2 / gm, zeros for cclip).
+    noise_var with an aggregator other than gm: the OMA pre-noise goes on a COPY of M, which
+    is what the aggregator sees: channel noise is not client state.  gm takes noise_var
+    through its options, as in SGD.  beta outside [0, 1) raises ValueError."""
+    if not 0 <= beta < 1:                     # (NaN fails the comparison too)
+        raise ValueError(f"beta must be in [0, 1) (got {beta!r})")
+
+    def train_eval():
+        return calculateAccuracy(model, loss_func, train_all, device) if eval_train else (0, 0)
+    assert byzantineSize == 0 or attack is not None
+    assert honestSize != 0
+    if layout not in ("rows", "panels"):
+        raise ValueError(f"layout must be 'rows' or 'panels' (got {layout!r})")
+    if fixSeed:
+        setup_seed(SEED)
+    K = honestSize + byzantineSize
+    device = device or torch.device("cpu")
+    DL = torch.utils.data.DataLoader
+
+    # SGD's shards, samplers and streams (the streams only carry the samplers' indices here)
+    n = len(train_dataset)
+    cuts = [(i * n) // K for i in range(K + 1)]
+    shards = [torch.utils.data.Subset(train_dataset, range(cuts[i], cuts[i + 1])) for i in range(K)]
+    train_all = DL(dataset=train_dataset, batch_size=batchSize, pin_memory=True, shuffle=False)
+    val_all = DL(dataset=validate_dataset, batch_size=batchSize, pin_memory=True, shuffle=False)
+    draws = rounds * displayInterval * batchSize
+    samplers = [torch.utils.data.sampler.RandomSampler(s, num_samples=draws, replacement=True)
+                for s in shards]
+    streams = [iter(DL(dataset=shards[i], batch_size=batchSize, sampler=samplers[i]))
+               for i in range(K)]
+
+    tl, ta = train_eval()
+    vl, va = calculateAccuracy(model, loss_func, val_all, device)
+    paths = {"train_loss": [tl], "train_acc": [ta], "val_loss": [vl], "val_acc": [va], "var": []}
+    if verbose:
+        _log(f"[0/{rounds}] train: loss={tl:.4f} acc={ta:.4f} val: loss={vl:.4f} acc={va:.4f}")
+
+    attack_name = attack.__name__ if attack is not None else None
+    params = list(model.parameters())
+    d = sum(p.numel() for p in params)
+    dev = params[0].device
+    panels = layout == "panels"
+    if panels:
+        from .panels import ClientPanels
+        M = ClientPanels(K, d, device=dev)                 # zero-filled
+    else:
+        M = torch.zeros(K, d, dtype=torch.float32, device=dev)
+    chain = _ClientChain.make(model, loss_func, train_dataset, cuts, batchSize, num_classes,
+                              device, client_kernel)
+    # beta as the fp32 the kernel is handed, so both paths apply one formula
+    beta = float(torch.tensor(beta, dtype=torch.float32))
+    omb = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(beta, dtype=torch.float32))
+    is_gm = aggregate.__name__ == "gm"
+    noisy = None
+    if noise_var is not None and not is_gm:
+        # the buffer of M's noisy copy
+        noisy = ClientPanels(K, d, device=dev, W=M.W, zero=False) if panels else torch.empty_like(M)
+    steps_left = rounds * displayInterval
+    nxt, R = None, None
+    for r in range(rounds):
+        for _ in range(displayInterval):
+            # the K batches, the samplers' index streams drawn in client order; with the
+            # kernel the next step's are drawn while this step runs on the device (as SGD)
+            cur = nxt if nxt is not None else _ClientChain.draw(streams)
+            if chain is not None:
+                chain.grads(cur, M, honestSize, attack_name, beta, weight_decay)
+                steps_left -= 1
+                nxt = _ClientChain.draw(streams) if steps_left > 0 else None
+            else:
+                theta = torch.cat([p.detach().reshape(-1) for p in params])
+                for node in range(K):
+                    xb, yb = torch.utils.data.default_collate(
+                        [shards[node][i] for i in cur[node].tolist()])
+                    xb, yb = xb.to(device), yb.to(device)
+                    if node >= honestSize and attack_name == "classflip":
+                        yb = (num_classes - 1) - yb
+                    elif node >= honestSize and attack_name == "dataflip":
+                        xb = 1.0 - xb
+                    grads = torch.autograd.grad(loss_func(model(xb), yb), params)
+                    g = torch.cat([t.reshape(-1) for t in grads]).add_(theta, alpha=weight_decay)
+                    m = (M.row(node) if panels else M[node]).mul(beta).add_(g, alpha=omb)
+                    if panels:
+                        M.store(node, m)
+                    else:
+                        M[node].copy_(m)
+            if attack is not None:
+                attack(M, byzantineSize)
+            options = {"maxiter": 1000, "tol": 1e-5, "eta": 1, "noise_var": noise_var,
+                       "guess": R, "honestSize": honestSize}
+            X = M
+            if noisy is not None:
+                X = noisy
+                (X.data if panels else X).copy_(M.data if panels else M)
+                if dev.type == "cpu" and panels:
+                    rows = X.to_rows()
+                    _oma_host(rows, noise_var)
+                    X.copy_rows_(rows)
+                elif dev.type == "cpu":
+                    _oma_host(X, noise_var)
+                else:
+                    from .aggregators import OMA
+                    OMA(X, noise_var)
+            R = aggregate(X, options)
+            off = 0
+            step = R.to(dev)
+            with torch.no_grad():
+                for p in params:
+                    p.sub_(step[off:off + p.numel()].view_as(p), alpha=gamma)
+                    off += p.numel()
+        paths["var"].append(getVarience(M, honestSize).cpu())
         tl, ta = train_eval()
         vl, va = calculateAccuracy(model, loss_func, val_all, device)
         for key, v in (("train_loss", tl), ("train_acc", ta), ("val_loss", vl), ("val_acc", va)):

@@ -764,6 +764,35 @@ int gm_client_chain_f32(gm_ctx* ctx, const float* data, int64_t ldd, const int64
                         int64_t honest, int32_t attack, float gamma, float weight_decay,
                         float* W, float* b, float* X, int64_t ldx, int32_t layout, void* stream);
 
+/* The K clients' stochastic gradients at ONE model, folded into their momenta: the worker-
+ * momentum loop in gradient space (Karimireddy, He & Jaggi, ICML 2021, Algorithm 1), as one
+ * stream-ordered kernel with one workgroup per client, for the model gm_client_chain_f32
+ * supports (MLP(F, C), CrossEntropyLoss mean, F <= 832, C <= 64, batch B <= 64).  For client k,
+ * with theta = [W (C*F, row-major), b (C)]:
+ *   g_k  = grad_theta meanCE(theta; batch k) + weight_decay * theta
+ *   M_k <- beta * M_k + (1 - beta) * g_k      (fmaf(beta, m, (1 - beta) * (g + wd * p)))
+ *   data, labels, idx, honest, attack   as gm_client_chain_f32's
+ *   beta     in [0, 1).  beta == 0: M is write-only (row k = g_k; what M held, NaN included,
+ *            does not reach the result)
+ *   W, b     the model's weight [C][F] and bias [C] (device), read only
+ *   M        the K x (C*F + C) momentum matrix, updated in place: GM_LAYOUT_ROWS (ldx = row
+ *            stride >= C*F + C, any alignment) or GM_LAYOUT_PANELS (ldx = panel stride
+ *            >= K*W, W = gm_panel_width(K)).  Nothing at or past column C*F + C of a row is
+ *            read or written (panel padding columns are not written).
+ * Row k depends only on (W, b, batch k, k >= honest, M_k): its bits are the same whatever K,
+ * the grid's schedule or the layout.
+ *
+ * GM_ERR_INVALID (nothing written): NULL pointers, K < 1 or K >= 2^31 (the grid), B < 1, F < 1,
+ * C < 1, ldd < F, honest outside [0, K], an unknown attack or layout, beta outside [0, 1) or
+ * NaN, ldx or the panel stride too small.
+ * GM_ERR_UNSUPPORTED (with a message): F, C or B beyond the limits, a panel layout whose K has
+ * no panel width. */
+int gm_client_grads_f32(gm_ctx*, const float* data, int64_t ldd, const int64_t* labels,
+                        int64_t F, int64_t C, const int32_t* idx /*[K][B]*/, int64_t K, int64_t B,
+                        int64_t honest, int32_t attack, float beta, float weight_decay,
+                        const float* W, const float* b, float* M, int64_t ldx, int32_t layout,
+                        void* stream);
+
 /* OMA with the reference's own draws (device arrays): h_re[K], h_im[K],
  * n_re[K*d], n_im[K*d] (row-major, already scaled by sqrt(noise_var)).
  * Bit-exact with the reference's fp32 op order. */
