@@ -72,6 +72,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes as C
+import functools
 import math
 import operator
 import os
@@ -242,52 +243,187 @@ def _stage(t: torch.Tensor, bf16_ok: bool = False) -> torch.Tensor:
 def _unit_rows(X: torch.Tensor):
     """(X or a contiguous copy, ldx): unit column stride, rows of the last two dimensions at
     least d apart."""
-    if X.stride(-1) != 1 or X.stride(-2) < X.shape[-1] or X.shape[-2] == 0:
+    d, ld = X.shape[-1], X.stride(-2)
+    if X.stride(-1) != 1 or ld < d or X.shape[-2] == 0:
         X = X.contiguous()
-    return X, max(X.stride(-2), X.shape[-1])
+        ld = X.stride(-2)
+    return X, max(ld, d)
 
 
-def _rows(X: torch.Tensor):
-    """(tensor, ldx) with unit column stride, rows >= d apart."""
-    if X.dim() != 2:
-        raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
-    return _unit_rows(X)
-
-
-def _fp32_panels(p: ClientPanels, who: str) -> ClientPanels:
-    if p.dtype != torch.float32:
-        raise TypeError(f"{who} is fp32 only (got {p.dtype} ClientPanels); gm2 / gm read bf16")
-    return p
-
-
-def _bf16_operand(X: torch.Tensor):
-    """(tensor, ldx, layout) of a bf16 [K, d] CUDA matrix for gm_weiszfeld_bf16: the rows
-    themselves where the kernel can read them (unit column stride, 16-byte aligned, d and the
-    row stride multiples of 8), else a packed copy in bf16 panels.  X is never written."""
-    if X.dim() != 2:
-        raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
-    K, d = X.shape
-    if (K > 0 and X.stride(1) == 1 and X.stride(0) >= d and X.stride(0) % 8 == 0 and d % 8 == 0
-            and X.data_ptr() % 16 == 0):
-        return X, X.stride(0), _lib.GM_LAYOUT_ROWS
-    P = ClientPanels.from_rows(X)
-    return P.data, P.panel_stride, _lib.GM_LAYOUT_PANELS
-
-
-def _client_operand(wList):
-    """(tensor, ldx, layout, K, d) of the client matrix the streaming pass reads (gm2, gm,
-    cclip): ClientPanels as they are, a bf16 [K, d] tensor through _bf16_operand, an fp32 one
-    through _rows; CPU tensors staged to the GPU.  wList is never written."""
+def _shape(wList, who: str, *, bf16: bool = False, max_k: int | None = None):
+    """(K, d) of the client matrix, after the checks that touch no device: a [K, d] tensor or
+    ClientPanels (ValueError), fp32 or, with `bf16`, bf16 (TypeError), 1 <= K <= max_k
+    (ValueError).  The entry points that promise to refuse before a GPU is touched call it
+    first."""
     if isinstance(wList, ClientPanels):
-        K, d = wList.shape
-        return wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS, K, d
-    if wList.dtype == torch.bfloat16:
-        K, d = wList.shape
-        X, ldx, layout = _bf16_operand(_stage(wList, bf16_ok=True))
-        return X, ldx, layout, K, d
-    X, ldx = _rows(_stage(wList))
+        K, d, dtype = wList.K, wList.d, wList.data.dtype
+    elif isinstance(wList, torch.Tensor) and wList.dim() == 2:
+        (K, d), dtype = wList.shape, wList.dtype
+    else:
+        got = tuple(wList.shape) if isinstance(wList, torch.Tensor) else type(wList).__name__
+        raise ValueError(f"{who}: the client matrix must be a [K, d] tensor or ClientPanels "
+                         f"(got {got})")
+    if dtype != torch.float32 and not (bf16 and dtype == torch.bfloat16):
+        raise TypeError(f"{who} reads fp32 or bf16 client updates (got {dtype})" if bf16 else
+                        f"{who} is fp32 only (got {dtype})")
+    if K < 1:
+        raise ValueError(f"{who}: the client matrix has no rows")
+    if max_k is not None and K > max_k:
+        raise ValueError(f"{who}: K <= {max_k} (got {K})")
+    return K, d
+
+
+def _operand(wList, *, bf16: bool = False):
+    """(tensor, ld, layout, K, d) of the client matrix as the library reads it, the one place
+    that pairs a layout with a tensor: ClientPanels as they are; a [K, d] tensor as rows, a CPU
+    tensor staged to the GPU and a non-unit or overlapping stride through a contiguous copy.
+    The tensor returned keeps such a copy alive, and ``is not wList`` tells that one was made
+    (an in-place caller copies back).  fp32 only unless `bf16`."""
+    if isinstance(wList, ClientPanels):
+        X = wList.data
+        if not bf16 and X.dtype != torch.float32:        # (_stage's refusal, for panels)
+            raise TypeError(f"aggregation kernels are fp32 (got {X.dtype})")
+        return X, wList.panel_stride, _lib.GM_LAYOUT_PANELS, wList.K, wList.d
+    X = _stage(wList, bf16)
+    if X.dim() != 2:
+        raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
+    X, ld = _unit_rows(X)
+    return (X, ld, _lib.GM_LAYOUT_ROWS, *X.shape)
+
+
+def _stream_operand(wList):
+    """_operand for the streaming pass (gm2, gm, cclip), whose bf16 kernel reads rows only where
+    it can load them 16 bytes at a time (unit column stride, 16-byte aligned, d and the row
+    stride multiples of 8): other bf16 rows are packed into bf16 panels first.  wList is never
+    written."""
+    if isinstance(wList, ClientPanels) or wList.dtype != torch.bfloat16:
+        return _operand(wList, bf16=True)
+    X = _stage(wList, True)
+    if X.dim() != 2:
+        raise ValueError(f"wList must be [K, d] (got {tuple(X.shape)})")
     K, d = X.shape
-    return X, ldx, _lib.GM_LAYOUT_ROWS, K, d
+    ld = X.stride(0)
+    if (K > 0 and X.stride(1) == 1 and ld >= d and ld % 8 == 0 and d % 8 == 0
+            and X.data_ptr() % 16 == 0):
+        return X, ld, _lib.GM_LAYOUT_ROWS, K, d
+    return _operand(ClientPanels.from_rows(X), bf16=True)
+
+
+def _twin(fn: str, layout: int) -> str:
+    """The ``*_panels_f32`` twin of the rows function `fn` (mean, median, trimmed_mean, Krum,
+    honest_variance, OMA: same results) where the operand is panels."""
+    return fn.replace("_f32", "_panels_f32") if layout == _lib.GM_LAYOUT_PANELS else fn
+
+
+@functools.lru_cache(maxsize=None)
+def _has_panels(K: int) -> bool:
+    """Whether K rows have a panel width (a fixed table of the library's: asked once per K)."""
+    return int(_lib.load().gm_panel_width(int(K))) > 0
+
+
+def _panels_out(layout, wList, K, who: str) -> bool:
+    """Whether a pre-step's rows go out as panels: `layout` is None (wList's own), "rows" or
+    "panels" (ValueError otherwise), and panels need a panel width for K rows (ValueError; K
+    None: not asked, as where a wrapper only validates its argument)."""
+    if layout not in (None, "rows", "panels"):
+        raise ValueError(f"{who}: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    panels = layout == "panels" or (layout is None and isinstance(wList, ClientPanels))
+    if panels and K is not None and not _has_panels(K):
+        raise ValueError(f"{who}: no panel layout for K = {K} rows (take them row-major)")
+    return panels
+
+
+def _new_rows(K: int, d: int, device, panels: bool):
+    """(out, Y, ldy, layout) of a fresh fp32 K x d output: `out` is what the caller gets, a
+    [K, d] tensor or ClientPanels(K, d), Y the tensor the library writes."""
+    if panels:
+        out = ClientPanels(K, d, device=device, zero=False)      # every column < d is written
+        return out, out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
+    out = torch.empty(K, d, dtype=torch.float32, device=device)
+    return out, out, max(d, 1), _lib.GM_LAYOUT_ROWS
+
+
+def _to_caller(out, wList):
+    """`out` on wList's device (a CPU wList was staged: its result goes back).  ClientPanels, a
+    pre-step's rows in the panel layout, stay on the GPU."""
+    if out.device == wList.device or isinstance(out, ClientPanels):
+        return out
+    return out.to(wList.device)
+
+
+def _index(x, who: str, what: str, lo: int, hi: int | None = None, kind=ValueError) -> int:
+    """x as an int in [lo, hi] (hi None: unbounded).  A bool, a float or a string is refused
+    with `kind`, a value out of range with ValueError."""
+    try:
+        if isinstance(x, bool):
+            raise TypeError
+        n = operator.index(x)
+    except TypeError:
+        n = None
+    if n is None or n < lo or (hi is not None and n > hi):
+        rng = f">= {lo}" if hi is None else f"in [{lo}, {hi}]"
+        if n is None:
+            raise kind(f"{who}: {what} must be an integer {rng} (got {x!r})")
+        raise ValueError(f"{who}: {what} = {n} not {rng}")
+    return n
+
+
+def _vector(v, d: int, device, what: str):
+    """v (a guess, a centre, the server's update) as contiguous fp32 of d elements on `device`;
+    None stays None."""
+    if v is None:
+        return None
+    if v.numel() != d:
+        raise ValueError(f"{what} has {v.numel()} elements, the rows have {d}")
+    return v.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _with_options(name: str, keys, make, doc: str):
+    """The ``with_options(**fixed)`` of the public callable `name`: keys outside `keys` are a
+    TypeError, ``make(fixed)`` (which refuses bad values) is the callable, returned under
+    `name` so that loops and logs that go by ``__name__`` see the rule's own."""
+    def with_options(**fixed):
+        unknown = sorted(set(fixed) - set(keys))
+        if unknown:
+            raise TypeError(f"{name}.with_options takes {', '.join(keys)} (got {unknown})")
+        fn = make(fixed)
+        fn.__name__ = fn.__qualname__ = name
+        # (a fixed tensor, fltrust's server_update, by its shape: its repr would read the device)
+        fn.__doc__ = f"{name} with " + ", ".join(
+            f"{k}={f'tensor{tuple(v.shape)}' if isinstance(v, torch.Tensor) else repr(v)}"
+            for k, v in fixed.items())
+        return fn
+    with_options.__doc__ = doc
+    return with_options
+
+
+def _fixed_options(name: str, check):
+    """make(fixed) for an ``aggregate(wList, options)``: `check(fixed)` now, then the fixed
+    options over the caller's at every call.  The aggregator is looked up by name when called."""
+    def make(fixed):
+        check(fixed)
+        return lambda wList, options={}: globals()[name](wList, {**(options or {}), **fixed})
+    return make
+
+
+def _pre_step(aggregate, suffix: str, doc: str, step):
+    """An ``aggregate(wList, options)`` that runs ``step(wList, options, its own name)`` -> (rows,
+    options), calls `aggregate` on them and returns the result on wList's device (a CPU wList's
+    rows stayed on the GPU as panels).  Named ``f"{aggregate.__name__}_{suffix}"``."""
+    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+        rows, opts = step(wList, options, agg.__name__)
+        out = aggregate(rows, opts)
+        # (whatever `aggregate` returns is handed on; only a tensor has a device to match)
+        return _to_caller(out, wList) if isinstance(out, torch.Tensor) else out
+    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_{suffix}"
+    agg.__doc__ = doc
+    return agg
+
+
+def _handover(layout, K: int):
+    """A wrapper's `layout` for K rows: "panels" falls back to "rows" where K has no panel
+    width."""
+    return "rows" if layout == "panels" and K >= 1 and not _has_panels(K) else layout
 
 
 def _noise_source(options) -> int:
@@ -385,26 +521,24 @@ def _weiszfeld(wList: torch.Tensor, options: dict, aircomp: bool):
             OMA(wList, float(pre_var), seed=pre_seed)
         last_result = GMResult(0, float("nan"), False, "none")
         return guess
-    X, ldx, layout, K, d = _client_operand(wList)
-    g0 = guess.detach().to(device=X.device, dtype=torch.float32).contiguous()
-    if g0.numel() != d:
-        raise ValueError(f"guess has {g0.numel()} elements, wList rows have {d}")
+    X, ldx, layout, K, d = _stream_operand(wList)
+    g0 = _vector(guess, d, X.device, "guess")
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     if d == 0:
         last_result = GMResult(1, 0.0, True, "none")
-        return out.to(wList.device)
+        return _to_caller(out, wList)
 
     o = _gm_opts(opts, aircomp, layout, pre_var, pre_seed, (K, d))
     res = _lib.GmResult()
-    context(X.device).call("gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32", X.data_ptr(), K, d,
-                           ldx, g0.data_ptr(), out.data_ptr(), C.byref(o), C.byref(res),
-                           _stream_ptr(X.device))
-    last_result = _result(res, None if bf16 else context(X.device))
+    ctx = context(X.device)
+    ctx.call("gm_weiszfeld_bf16" if bf16 else "gm_weiszfeld_f32", X.data_ptr(), K, d, ldx,
+             g0.data_ptr(), out.data_ptr(), C.byref(o), C.byref(res), _stream_ptr(X.device))
+    last_result = _result(res, None if bf16 else ctx)
     if pre_var is not None and not isinstance(wList, ClientPanels) and X is not wList:
         # a strided view was packed into a copy: the fused pre-noise landed in the
         # copy, and OMA's contract is in place on wList (M:351-352, as OMA() copies back)
         wList.copy_(X)
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
 def gm2(wList, options={}):  # noqa: B006 - the reference's signature (M:162)
@@ -475,19 +609,16 @@ def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
     global last_result
     options = options or {}
     params = _cclip_params(options)
-    if not isinstance(wList, ClientPanels) and wList.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"cclip reads fp32 or bf16 client updates (got {wList.dtype})")
+    _, d = _shape(wList, "cclip", bf16=True)
     guess = options.get("guess")
     if guess is None:
-        guess = torch.zeros(wList.shape[1], dtype=torch.float32, device=wList.device)
+        guess = torch.zeros(d, dtype=torch.float32, device=wList.device)
     if params[1] == 0:
         last_result = GMResult(0, float("nan"), False, "none")
         cclip.last_info = {"clipped": 0}
         return guess
-    X, ldx, layout, K, d = _client_operand(wList)
-    g0 = guess.detach().to(device=X.device, dtype=torch.float32).contiguous()
-    if g0.numel() != d:
-        raise ValueError(f"guess has {g0.numel()} elements, wList rows have {d}")
+    X, ldx, layout, K, d = _stream_operand(wList)
+    g0 = _vector(guess, d, X.device, "guess")
     if d == 0:
         last_result = GMResult(1, 0.0, True, "none")
         cclip.last_info = {"clipped": 0}
@@ -496,46 +627,27 @@ def cclip(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
         context(X.device), X.data_ptr(), X.dtype == torch.bfloat16, K, d, ldx, layout, g0, params,
         int(options.get("check_every", 0)))
     cclip.last_info = {"clipped": clipped}
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
-def _cclip_with_options(**fixed):
+cclip.with_options = _with_options(
+    "cclip", _CCLIP_KEYS,
+    # (bad values fail when the options are fixed; tau may still come from the caller's)
+    _fixed_options("cclip", lambda fixed: _cclip_params(fixed if "tau" in fixed
+                                                        else dict(fixed, tau=1.0))),
     """An ``aggregate(wList, options)`` callable named "cclip" that applies tau / clip_iters /
     clip_tol over the caller's options, for loops that build the dict themselves
     (training.run(..., aggregate=cclip.with_options(tau=10.0)), the reference's
-    eval(args.agg))."""
-    unknown = sorted(set(fixed) - set(_CCLIP_KEYS))
-    if unknown:
-        raise TypeError(f"cclip.with_options takes {', '.join(_CCLIP_KEYS)} (got {unknown})")
-    _cclip_params(fixed if "tau" in fixed else dict(fixed, tau=1.0))   # bad values fail here
-
-    def aggregate(wList, options={}):  # noqa: B006
-        return cclip(wList, {**(options or {}), **fixed})
-    aggregate.__name__ = aggregate.__qualname__ = "cclip"
-    aggregate.__doc__ = f"cclip with {fixed}"
-    return aggregate
-
-
-cclip.with_options = _cclip_with_options
+    eval(args.agg)).""")
 cclip.last_info = {"clipped": 0}
 
 
-def _fp32_operand(wList, who: str, fn: str):
-    """(tensor, ldx, K, d, function) of an fp32-only aggregator's client matrix: rows (CPU
-    tensors staged) for `fn`, fp32 ClientPanels for its *_panels_f32 twin (same results)."""
-    if isinstance(wList, ClientPanels):
-        _fp32_panels(wList, who)
-        return (wList.data, wList.panel_stride, *wList.shape, fn.replace("_f32", "_panels_f32"))
-    X, ldx = _rows(_stage(wList))
-    return (X, ldx, *X.shape, fn)
-
-
 def _coordinate(wList, fn_name, *extra):
-    X, ldx, K, d, fn_name = _fp32_operand(wList, fn_name[3:-4], fn_name)
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
-    context(X.device).call(fn_name, X.data_ptr(), K, d, ldx, *extra, out.data_ptr(),
-                           _stream_ptr(X.device))
-    return out if wList.device == out.device else out.to(wList.device)
+    context(X.device).call(_twin(fn_name, layout), X.data_ptr(), K, d, ldx, *extra,
+                           out.data_ptr(), _stream_ptr(X.device))
+    return _to_caller(out, wList)
 
 
 def mean(wList, options={}):  # noqa: B006 - reference signature (M:186)
@@ -556,45 +668,19 @@ def trimmed_mean(wList, options={}):  # noqa: B006 - reference signature (M:189)
 def Krum(wList, options):  # noqa: N802 - reference name (M:197)
     """The row with the smallest sum of squared distances to its honestSize-1
     nearest rows, itself included (M:197-204)."""
-    X, ldx, K, d, fn = _fp32_operand(wList, "Krum", "gm_krum_f32")
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     idx = C.c_int64()
     ctx = context(X.device)
-    ctx.call(fn, X.data_ptr(), K, d, ldx, int(options["honestSize"]), out.data_ptr(),
-             C.byref(idx), _stream_ptr(X.device))
+    ctx.call(_twin("gm_krum_f32", layout), X.data_ptr(), K, d, ldx, int(options["honestSize"]),
+             out.data_ptr(), C.byref(idx), _stream_ptr(X.device))
     info = (C.c_int64 * 3)()
     _lib.check(ctx.lib.gm_krum_last_info(ctx.handle, info), "gm_krum_last_info")
     Krum.last_index = idx.value
     Krum.last_info = {"algo": ("exact", "gram")[info[0]], "candidates": info[1],
                       "reason": ("ok", "not_chosen", "not_eligible", "gram_nonfinite",
                                  "candidates")[info[2]]}
-    return out if wList.device == out.device else out.to(wList.device)
-
-
-def _robust_operand(wList, who: str):
-    """(tensor, ldx, layout, K, d) of the client matrix of meamed / multi_krum / bulyan: an
-    fp32 [K, d] tensor (a CPU tensor staged) or fp32 ClientPanels.  Call _robust_shape first:
-    it refuses other inputs before anything touches a GPU."""
-    if isinstance(wList, ClientPanels):
-        _fp32_panels(wList, who)
-        return (wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS, *wList.shape)
-    X, ldx = _rows(_stage(wList))
-    return (X, ldx, _lib.GM_LAYOUT_ROWS, *X.shape)
-
-
-def _robust_shape(wList, who: str):
-    """(K, d) of an fp32 [K, d] tensor or fp32 ClientPanels; TypeError for another dtype (bf16
-    is read by gm2 / gm / cclip / bucketing only), ValueError for another shape."""
-    if isinstance(wList, ClientPanels):
-        _fp32_panels(wList, who)
-    elif not isinstance(wList, torch.Tensor) or wList.dtype != torch.float32:
-        raise TypeError(f"{who} is fp32 only (got {getattr(wList, 'dtype', type(wList))})")
-    elif wList.dim() != 2:
-        raise ValueError(f"wList must be [K, d] (got {tuple(wList.shape)})")
-    K, d = (int(n) for n in wList.shape)
-    if K < 1:
-        raise ValueError(f"{who}: wList has no rows")
-    return K, d
+    return _to_caller(out, wList)
 
 
 def _honest_size(options, who: str) -> int:
@@ -610,17 +696,15 @@ def meamed(wList, options):
     the column gives NaN).  One HIP pass that reads wList once (robust.hip col_meamed).
     wList: an fp32 [K, d] tensor or fp32 ClientPanels, K <= 1024, 1 <= honestSize <= K; the
     result is fp32 on wList.device."""
-    K, d = _robust_shape(wList, "meamed")
+    K, d = _shape(wList, "meamed", max_k=1024)
     keep = _honest_size(options, "meamed")
     if not 1 <= keep <= K:
         raise ValueError(f"meamed: honestSize {keep} not in [1, {K}]")
-    if K > 1024:
-        raise ValueError(f"meamed: K <= 1024 (got {K})")
-    X, ldx, layout, K, d = _robust_operand(wList, "meamed")
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     context(X.device).call("gm_meamed_f32", X.data_ptr(), K, d, ldx, layout, None, K, keep,
                            out.data_ptr(), _stream_ptr(X.device))
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
 def multi_krum(wList, options):
@@ -631,7 +715,7 @@ def multi_krum(wList, options):
     that Krum row bit for bit.  wList: an fp32 [K, d] tensor or fp32 ClientPanels, K <= 4096,
     2 <= honestSize <= K + 1, 1 <= m <= K.  ``multi_krum.last_selected`` holds the selected
     rows, increasing."""
-    K, d = _robust_shape(wList, "multi_krum")
+    K, d = _shape(wList, "multi_krum", max_k=4096)
     honest = _honest_size(options, "multi_krum")
     if not 2 <= honest <= K + 1:
         raise ValueError(f"multi_krum: honestSize {honest} not in [2, {K + 1}]")
@@ -639,16 +723,14 @@ def multi_krum(wList, options):
     m = honest if m is None else int(m)
     if not 1 <= m <= K:
         raise ValueError(f"multi_krum: m = {m} not in [1, {K}]")
-    if K > 4096:
-        raise ValueError(f"multi_krum: K <= 4096 (got {K})")
-    X, ldx, layout, K, d = _robust_operand(wList, "multi_krum")
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     sel = (C.c_int32 * m)()
     if d > 0:
         context(X.device).call("gm_multi_krum_f32", X.data_ptr(), K, d, ldx, layout, honest, m,
                                out.data_ptr(), sel, _stream_ptr(X.device))
     multi_krum.last_selected = list(sel) if d > 0 else []
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
 multi_krum.last_selected = None
@@ -663,16 +745,14 @@ def bulyan(wList, options):
     rows keeping theta - 2f values per coordinate (f == 0: the column mean).  wList: an fp32
     [K, d] tensor or fp32 ClientPanels, K <= 1024.  ``bulyan.last_selected`` holds the
     selected rows in selection order."""
-    K, d = _robust_shape(wList, "bulyan")
+    K, d = _shape(wList, "bulyan", max_k=1024)
     honest = _honest_size(options, "bulyan")
     f = K - honest
     if honest < 1 or f < 0:
         raise ValueError(f"bulyan: honestSize {honest} not in [1, {K}]")
     if K < 4 * f + 3:
         raise ValueError(f"bulyan: K = {K} < 4f + 3 = {4 * f + 3} with f = K - honestSize = {f}")
-    if K > 1024:
-        raise ValueError(f"bulyan: K <= 1024 (got {K})")
-    X, ldx, layout, K, d = _robust_operand(wList, "bulyan")
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     theta = K - 2 * f
     sel = (C.c_int32 * theta)()
@@ -680,30 +760,17 @@ def bulyan(wList, options):
         context(X.device).call("gm_bulyan_f32", X.data_ptr(), K, d, ldx, layout, honest,
                                out.data_ptr(), sel, _stream_ptr(X.device))
     bulyan.last_selected = list(sel) if d > 0 else []
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
 bulyan.last_selected = None
-
-
-def _bucket_size(s) -> int:
-    """s as an int >= 1; ValueError otherwise (a float, a bool, 0, ...)."""
-    try:
-        if isinstance(s, bool):
-            raise TypeError
-        n = operator.index(s)
-    except TypeError:
-        raise ValueError(f"bucketing: s must be an integer >= 1 (got {s!r})") from None
-    if n < 1:
-        raise ValueError(f"bucketing: s must be >= 1 (got {s!r})")
-    return n
 
 
 def _assignment(K: int, s: int, generator=None) -> torch.Tensor:
     """The random assignment of K clients to ceil(K/s) buckets: ``torch.randperm(K)``, one
     draw from `generator` (the global CPU generator when None).  Bucket i holds clients
     ``perm[i*s : (i+1)*s]``."""
-    _bucket_size(s)
+    _index(s, "bucketing", "s", 1)
     return torch.randperm(int(K), generator=generator)
 
 
@@ -743,33 +810,16 @@ def bucketing(wList, s, perm=None, generator=None, layout=None):
 
     d-sharded clients (ShardedGM): bucketing is column-local, so each rank buckets its own
     shard with the SAME perm and hands the result to ``ShardedGM.gm2`` / ``.cclip``."""
-    s = _bucket_size(s)
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"bucketing: layout must be None, 'rows' or 'panels' (got {layout!r})")
-    panels_in = isinstance(wList, ClientPanels)
-    if not panels_in and (not isinstance(wList, torch.Tensor) or wList.dim() != 2):
-        raise ValueError("bucketing: wList must be a [K, d] tensor or ClientPanels")
-    if wList.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"bucketing reads fp32 or bf16 client updates (got {wList.dtype})")
+    s = _index(s, "bucketing", "s", 1)
+    K, d = _shape(wList, "bucketing", bf16=True)
+    # (the Kb bucket means: a Kb without a panel width is refused where the panels are made)
+    panels_out = _panels_out(layout, wList, None, "bucketing")
     if s == 1:
         return wList
-    K, d = (int(n) for n in wList.shape)
-    if K < 1:
-        raise ValueError("bucketing: wList has no rows")
     p = _bucket_perm(perm, K) if perm is not None else _assignment(K, s, generator)
     bucketing.last_perm = p
-    if panels_in:
-        X, ldx, lin = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
-        lin = _lib.GM_LAYOUT_ROWS
-    Kb = -(-K // s)
-    if layout == "panels" or (layout is None and panels_in):
-        out = ClientPanels(Kb, d, device=X.device, zero=False)   # every column < d is written
-        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        out = Y = torch.empty(Kb, d, dtype=torch.float32, device=X.device)
-        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    X, ldx, lin, K, d = _operand(wList, bf16=True)
+    out, Y, ldy, lout = _new_rows(-(-K // s), d, X.device, panels_out)
     if d > 0:
         # (pdev goes back to torch's caching allocator, which reuses it in stream order)
         pdev = p.to(device=X.device, dtype=torch.int32)
@@ -777,9 +827,7 @@ def bucketing(wList, s, perm=None, generator=None, layout=None):
             "gm_bucket_means_bf16" if X.dtype == torch.bfloat16 else "gm_bucket_means_f32",
             X.data_ptr(), K, d, ldx, lin, pdev.data_ptr(), s, Y.data_ptr(), ldy, lout,
             _stream_ptr(X.device))
-    if out is Y and wList.device != Y.device:
-        return Y.to(wList.device)
-    return out
+    return _to_caller(out, wList)
 
 
 bucketing.assignment = _assignment
@@ -800,48 +848,25 @@ def bucketed(aggregate, s, generator=None, layout="panels"):
     ``honestSize' = ceil(K/s) - B`` (ValueError if that is < 2: s is too large for this many
     Byzantine clients).  The caller's dict is not modified.  ``s == 1`` calls `aggregate`
     directly.  The result lives on wList.device, as the aggregators' own."""
-    s = _bucket_size(s)
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"bucketed: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    s = _index(s, "bucketed", "s", 1)
+    _panels_out(layout, None, None, "bucketed")
 
-    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+    def step(wList, options, name):
         if s == 1:
-            return aggregate(wList, options)
+            return wList, options
         K = int(wList.shape[0])
         Kb = -(-K // s)
-        opts = options
         if options and options.get("honestSize") is not None:
             inner = Kb - (K - int(options["honestSize"]))
             if inner < 2:
                 raise ValueError(
-                    f"{agg.__name__}: {K - int(options['honestSize'])} Byzantine clients leave "
+                    f"{name}: {K - int(options['honestSize'])} Byzantine clients leave "
                     f"honestSize' = {inner} of {Kb} buckets (needs >= 2): use a smaller s")
-            opts = dict(options, honestSize=inner)
-        out = aggregate(bucketing(wList, s, generator=generator, layout=layout), opts)
-        if isinstance(out, torch.Tensor) and out.device != wList.device:
-            out = out.to(wList.device)        # (a CPU wList's means stayed on the GPU as panels)
-        return out
+            options = dict(options, honestSize=inner)
+        return bucketing(wList, s, generator=generator, layout=layout), options
 
-    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_b{s}"
-    agg.__doc__ = f"{aggregate.__name__} on the bucket means of s = {s} bucketing"
-    return agg
-
-
-def _nnm_f(f, K: int, who: str) -> int:
-    """f as an int in [0, K - 1]; ValueError otherwise (a float, a bool, out of range)."""
-    try:
-        if isinstance(f, bool):
-            raise TypeError
-        n = operator.index(f)
-    except TypeError:
-        raise ValueError(f"{who}: f must be an integer in [0, {K - 1}] (got {f!r})") from None
-    if not 0 <= n <= K - 1:
-        raise ValueError(f"{who}: f = {n} not in [0, {K - 1}]")
-    return n
-
-
-def _has_panels(K: int) -> bool:
-    return int(_lib.load().gm_panel_width(int(K))) > 0
+    return _pre_step(aggregate, f"b{s}",
+                     f"{aggregate.__name__} on the bucket means of s = {s} bucketing", step)
 
 
 def nnm(wList, f, layout=None, neighbors=False):
@@ -863,31 +888,19 @@ def nnm(wList, f, layout=None, neighbors=False):
     for ClientPanels; ``"rows"`` / ``"panels"`` force one.  ``neighbors=True`` returns
     ``(Y, N)`` with N the int32 [K, K - f] neighbour lists (increasing within a row) on the GPU.
     bf16 inputs, d-sharded contexts and K > 4096 are refused."""
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"nnm: layout must be None, 'rows' or 'panels' (got {layout!r})")
-    K, d = _robust_shape(wList, "nnm")
-    f = _nnm_f(f, K, "nnm")
-    if K > 4096:
-        raise ValueError(f"nnm: K <= 4096 (got {K})")
-    panels_out = layout == "panels" or (layout is None and isinstance(wList, ClientPanels))
-    if panels_out and not _has_panels(K):
-        raise ValueError(f"nnm: no panel layout for K = {K} rows (take them row-major)")
-    X, ldx, lin, K, d = _robust_operand(wList, "nnm")
+    K, d = _shape(wList, "nnm", max_k=4096)
+    f = _index(f, "nnm", "f", 0, K - 1)
+    panels_out = _panels_out(layout, wList, K, "nnm")
+    X, ldx, lin, K, d = _operand(wList)
     m = K - f
-    if panels_out:
-        out = ClientPanels(K, d, device=X.device, zero=False)    # every column < d is written
-        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        out = Y = torch.empty(K, d, dtype=torch.float32, device=X.device)
-        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    out, Y, ldy, lout = _new_rows(K, d, X.device, panels_out)
     N = torch.empty(K, m, dtype=torch.int32, device=X.device) if neighbors else None
     if d > 0:
         context(X.device).call("gm_nnm_f32", X.data_ptr(), K, d, ldx, lin, f, Y.data_ptr(), ldy,
                                lout, N.data_ptr() if neighbors else None, _stream_ptr(X.device))
     elif neighbors:                      # every distance is 0: the m rows of lowest index
         N.copy_(torch.arange(m, dtype=torch.int32, device=X.device).expand(K, m))
-    if out is Y and wList.device != Y.device:
-        out = Y.to(wList.device)
+    out = _to_caller(out, wList)
     return (out, N) if neighbors else out
 
 
@@ -902,24 +915,15 @@ def mixed(aggregate, f=None, layout="panels"):
     per call (ValueError without it).  Options pass through unchanged (NNM keeps all K rows, so
     ``honestSize`` stands); the caller's dict is not modified.  The result lives on
     wList.device, as the aggregators' own."""
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"mixed: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    _panels_out(layout, None, None, "mixed")
 
-    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+    def step(wList, options, name):
         K = int(wList.shape[0])
-        if f is None:
-            f_ = K - _honest_size(options, agg.__name__)
-        else:
-            f_ = f
-        lay = "rows" if layout == "panels" and K >= 1 and not _has_panels(K) else layout
-        out = aggregate(nnm(wList, f_, layout=lay), options)
-        if isinstance(out, torch.Tensor) and out.device != wList.device:
-            out = out.to(wList.device)        # (a CPU wList's mixed rows stayed on the GPU as panels)
-        return out
+        f_ = f if f is not None else K - _honest_size(options, name)
+        return nnm(wList, f_, layout=_handover(layout, K)), options
 
-    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_nnm"
-    agg.__doc__ = f"{aggregate.__name__} on the rows mixed by nearest-neighbor mixing"
-    return agg
+    return _pre_step(aggregate, "nnm",
+                     f"{aggregate.__name__} on the rows mixed by nearest-neighbor mixing", step)
 
 
 _DNC_KEYS = ("dnc_iters", "dnc_dims", "dnc_c", "dnc_columns", "generator", "power_iters",
@@ -1005,14 +1009,14 @@ def dnc(wList, options):
     q == 0: nothing is drawn), ``dnc.last_selected`` the good rows, increasing,
     ``dnc.last_scores`` the fp64 [dnc_iters, K] scores on the GPU and ``dnc.last_info``
     ``{"removed": q, "power_iters": [...], "converged": [...]}`` per round."""
-    K, d = _robust_shape(wList, "dnc")
+    K, d = _shape(wList, "dnc", max_k=4096)
     honest = _honest_size(options, "dnc")
     iters, b, c, pit, ptol = _dnc_scalars(options)
     f = K - honest
     if honest < 1 or f < 0:
         raise ValueError(f"dnc: honestSize {honest} not in [1, {K}]")
-    if not 2 <= K <= 4096:
-        raise ValueError(f"dnc: 2 <= K <= 4096 (got {K})")
+    if K < 2:
+        raise ValueError(f"dnc: K >= 2 (got {K})")
     q = int(c * f)
     if q * iters >= K:
         raise ValueError(f"dnc: q * dnc_iters = {q} * {iters} >= K = {K} rows would be removed")
@@ -1024,7 +1028,7 @@ def dnc(wList, options):
         if K * cols.shape[1] > _DNC_MAX_ELEMS:
             raise ValueError(f"dnc: K * n = {K} * {cols.shape[1]} sampled elements exceed 2^27: "
                              "lower dnc_dims")
-    X, ldx, layout, K, d = _robust_operand(wList, "dnc")
+    X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     scores = torch.zeros(iters, K, dtype=torch.float64, device=X.device)
     good, n_good = (C.c_int32 * K)(*range(K)), C.c_int64(K)
@@ -1040,27 +1044,15 @@ def dnc(wList, options):
     dnc.last_selected = list(good[:n_good.value])
     dnc.last_scores = scores
     dnc.last_info = {"removed": q, "power_iters": list(nit), "converged": [bool(x) for x in conv]}
-    return out if wList.device == out.device else out.to(wList.device)
-
-
-def _dnc_with_options(**fixed):
-    """An ``aggregate(wList, options)`` callable named "dnc" that applies the given dnc options
-    over the caller's, for loops that build the dict themselves
-    (training.run(..., aggregate=dnc.with_options(dnc_c=1.5, dnc_iters=3)))."""
-    unknown = sorted(set(fixed) - set(_DNC_KEYS))
-    if unknown:
-        raise TypeError(f"dnc.with_options takes {', '.join(_DNC_KEYS)} (got {unknown})")
-    _dnc_scalars(fixed)                                    # bad values fail here
-
-    def aggregate(wList, options={}):  # noqa: B006
-        return dnc(wList, {**(options or {}), **fixed})
-    aggregate.__name__ = aggregate.__qualname__ = "dnc"
-    aggregate.__doc__ = f"dnc with {fixed}"
-    return aggregate
+    return _to_caller(out, wList)
 
 
 dnc.columns = _dnc_draw
-dnc.with_options = _dnc_with_options
+dnc.with_options = _with_options(
+    "dnc", _DNC_KEYS, _fixed_options("dnc", _dnc_scalars),
+    """An ``aggregate(wList, options)`` callable named "dnc" that applies the given dnc options
+    over the caller's, for loops that build the dict themselves
+    (training.run(..., aggregate=dnc.with_options(dnc_c=1.5, dnc_iters=3))).""")
 dnc.last_columns = dnc.last_selected = dnc.last_scores = dnc.last_info = None
 
 
@@ -1084,40 +1076,20 @@ def _fltrust_server(options, K=None, d=None):
         if d is not None and su.numel() != d:
             raise ValueError(f"server_update has {su.numel()} elements, wList rows have {d}")
         return su, -1
-    try:
-        if isinstance(sr, bool):
-            raise TypeError
-        row = operator.index(sr)
-    except TypeError:
-        raise TypeError(f"fltrust: server_row must be an integer (got {sr!r})") from None
-    if row < 0 or (K is not None and row >= K):
-        raise ValueError(f"fltrust: server_row = {row} not in [0, {K if K is not None else 'K'})")
-    return None, row
+    # (a server_row that is no integer is a TypeError, as a server_update that is no tensor)
+    return None, _index(sr, "fltrust", "server_row", 0, None if K is None else K - 1, TypeError)
 
 
-def _fltrust_shape(wList, who: str = "fltrust"):
-    """(K, d) of an fp32 or bf16 [K, d] tensor or ClientPanels, K in [1, 2048]; TypeError /
-    ValueError otherwise, before anything touches a GPU."""
-    if not isinstance(wList, ClientPanels) and (not isinstance(wList, torch.Tensor)
-                                                or wList.dim() != 2):
-        raise ValueError(f"{who}: wList must be a [K, d] tensor or ClientPanels")
-    if wList.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{who} reads fp32 or bf16 client updates (got {wList.dtype})")
-    K, d = (int(n) for n in wList.shape)
-    if K < 1:
-        raise ValueError(f"{who}: wList has no rows")
-    if K > _FLTRUST_MAX_K:
-        raise ValueError(f"{who}: K <= {_FLTRUST_MAX_K} (got {K})")
-    return K, d
-
-
-def _fltrust_vec(v, d: int, device, what: str):
-    """v as a contiguous fp32 [d] vector on `device` (None stays None)."""
-    if v is None:
-        return None
-    if v.numel() != d:
-        raise ValueError(f"{what} has {v.numel()} elements, wList rows have {d}")
-    return v.detach().reshape(-1).to(device=device, dtype=torch.float32).contiguous()
+def _fltrust_args(wList, options, who: str, bf16: bool = True):
+    """(K, d, server_update or None, server_row or -1, guess or None) of an fltrust call, checked
+    before anything touches a GPU (ShardedGM.fltrust reads fp32 shards only)."""
+    options = options or {}
+    K, d = _shape(wList, who, bf16=bf16, max_k=_FLTRUST_MAX_K)
+    su, row = _fltrust_server(options, K, d)
+    guess = options.get("guess")
+    if guess is not None and guess.numel() != d:
+        raise ValueError(f"guess has {guess.numel()} elements, the rows have {d}")
+    return K, d, su, row, guess
 
 
 def _run_fltrust(ctx, X, K: int, d: int, ldx: int, layout: int, server, row: int, centre):
@@ -1169,62 +1141,25 @@ def fltrust(wList, options):
     trusted rows; no host synchronisation.  ``fltrust.last_info`` holds the by-products as views
     of one device buffer: ``cos``, ``norm2`` (||u_k||^2) and ``trust`` (TS_k) as fp64 [K],
     ``server_norm2`` and ``trust_sum`` as 0-dim tensors."""
-    options = options or {}
-    K, d = _fltrust_shape(wList)
-    su, row = _fltrust_server(options, K, d)
-    guess = options.get("guess")
-    if guess is not None and guess.numel() != d:
-        raise ValueError(f"guess has {guess.numel()} elements, wList rows have {d}")
-    if isinstance(wList, ClientPanels):
-        X, ldx, layout = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
-        layout = _lib.GM_LAYOUT_ROWS
-    server = _fltrust_vec(su, d, X.device, "server_update")
-    centre = _fltrust_vec(guess, d, X.device, "guess")
+    K, d, su, row, guess = _fltrust_args(wList, options, "fltrust")
+    X, ldx, layout, K, d = _operand(wList, bf16=True)
+    server = _vector(su, d, X.device, "server_update")
+    centre = _vector(guess, d, X.device, "guess")
     out, stats = _run_fltrust(context(X.device), X, K, d, ldx, layout, server, row, centre)
     fltrust.last_info = _fltrust_info(stats, K)
-    return out if wList.device == out.device else out.to(wList.device)
+    return _to_caller(out, wList)
 
 
-def _fltrust_with_options(**fixed):
+fltrust.with_options = _with_options(
+    "fltrust", _FLTRUST_KEYS, _fixed_options("fltrust", _fltrust_server),
     """An ``aggregate(wList, options)`` callable named "fltrust" that applies server_update /
     server_row over the caller's options, for loops that build the dict themselves
     (training.run(..., aggregate=fltrust.with_options(server_row=0)): client 0's shard is the
-    root dataset)."""
-    unknown = sorted(set(fixed) - set(_FLTRUST_KEYS))
-    if unknown:
-        raise TypeError(f"fltrust.with_options takes {', '.join(_FLTRUST_KEYS)} (got {unknown})")
-    _fltrust_server(fixed)                                 # bad values fail here
-
-    def aggregate(wList, options={}):  # noqa: B006
-        return fltrust(wList, {**(options or {}), **fixed})
-    aggregate.__name__ = aggregate.__qualname__ = "fltrust"
-    aggregate.__doc__ = f"fltrust with {sorted(fixed)}"
-    return aggregate
-
-
-fltrust.with_options = _fltrust_with_options
+    root dataset).""")
 fltrust.last_info = None
 
 
 _CLIP_MAX_K = 4096                # gm_clip_rows_f32 / _bf16's cap on K
-
-
-def _clip_shape(wList, who: str):
-    """(K, d) of an fp32 or bf16 [K, d] tensor or ClientPanels, K in [1, 4096]; TypeError /
-    ValueError otherwise, before anything touches a GPU."""
-    if not isinstance(wList, ClientPanels) and (not isinstance(wList, torch.Tensor)
-                                                or wList.dim() != 2):
-        raise ValueError(f"{who}: wList must be a [K, d] tensor or ClientPanels")
-    if wList.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{who} reads fp32 or bf16 client updates (got {wList.dtype})")
-    K, d = (int(n) for n in wList.shape)
-    if K < 1:
-        raise ValueError(f"{who}: wList has no rows")
-    if K > _CLIP_MAX_K:
-        raise ValueError(f"{who}: K <= {_CLIP_MAX_K} (got {K})")
-    return K, d
 
 
 def _clip_tau(tau, who: str) -> float:
@@ -1248,6 +1183,17 @@ def _clip_centre(centre, d: int, who: str):
     return centre
 
 
+def _clip_args(wList, who: str, rule: int, f, tau, centre, bf16: bool = True):
+    """(K, d, f, tau, centre) of a clip / arc call, checked before anything touches a GPU
+    (ShardedGM.clip / .arc read fp32 shards only)."""
+    K, d = _shape(wList, who, bf16=bf16, max_k=_CLIP_MAX_K)
+    if rule == _lib.GM_CLIP_ARC:
+        f, tau = _index(f, who, "f", 0, K - 1), 0.0
+    else:
+        f, tau = 0, _clip_tau(tau, who)
+    return K, d, f, tau, _clip_centre(centre, d, who)
+
+
 def _clip_info(stats, K: int):
     return {"norm2": stats[:K], "scale": stats[K:2 * K], "threshold2": stats[2 * K],
             "clipped": stats[2 * K + 1]}
@@ -1257,14 +1203,7 @@ def _run_clip(ctx, X, K: int, d: int, ldx: int, lin: int, centre, rule: int, f: 
               panels_out: bool, inplace: bool = False):
     """gm_clip_rows_f32 / _bf16 on ctx: (the clipped rows, stats [2K + 2] fp64) on X's device.
     The rows are a [K, d] tensor or ClientPanels(K, d), or None in place (X holds them)."""
-    if inplace:
-        out, Y, ldy, lout = None, X, ldx, lin
-    elif panels_out:
-        out = ClientPanels(K, d, device=X.device, zero=False)    # every column < d is written
-        Y, ldy, lout = out.data, out.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        out = Y = torch.empty(K, d, dtype=torch.float32, device=X.device)
-        ldy, lout = max(d, 1), _lib.GM_LAYOUT_ROWS
+    out, Y, ldy, lout = (None, X, ldx, lin) if inplace else _new_rows(K, d, X.device, panels_out)
     stats = torch.zeros(2 * K + 2, dtype=torch.float64, device=X.device)
     if d > 0:
         ctx.call("gm_clip_rows_bf16" if X.dtype == torch.bfloat16 else "gm_clip_rows_f32",
@@ -1278,30 +1217,18 @@ def _run_clip(ctx, X, K: int, d: int, ldx: int, lin: int, centre, rule: int, f: 
 
 def _clip(fn, wList, rule: int, f, tau, centre, layout, inplace: bool):
     who = fn.__name__
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"{who}: layout must be None, 'rows' or 'panels' (got {layout!r})")
-    K, d = _clip_shape(wList, who)
-    if rule == _lib.GM_CLIP_ARC:
-        f, tau = _nnm_f(f, K, who), 0.0
-    else:
-        f, tau = 0, _clip_tau(tau, who)
-    centre = _clip_centre(centre, d, who)
+    K, d, f, tau, centre = _clip_args(wList, who, rule, f, tau, centre)
     panels_in = isinstance(wList, ClientPanels)
-    panels_out = layout == "panels" or (layout is None and panels_in)
+    # (in place the rows stay where they are: no panel width is asked of K)
+    panels_out = _panels_out(layout, wList, None if inplace else K, who)
     if inplace:
         if wList.dtype != torch.float32:
             raise TypeError(f"{who}: inplace=True needs fp32 rows (got {wList.dtype}: the "
                             "clipped rows are fp32)")
         if panels_out != panels_in:
             raise ValueError(f"{who}: inplace=True keeps wList's own layout (got {layout!r})")
-    elif panels_out and not _has_panels(K):
-        raise ValueError(f"{who}: no panel layout for K = {K} rows (take them row-major)")
-    if panels_in:
-        X, ldx, lin = wList.data, wList.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        X, ldx = _unit_rows(_stage(wList, bf16_ok=True))
-        lin = _lib.GM_LAYOUT_ROWS
-    c = _fltrust_vec(centre, d, X.device, "centre")
+    X, ldx, lin, K, d = _operand(wList, bf16=True)
+    c = _vector(centre, d, X.device, "centre")
     out, stats = _run_clip(context(X.device), X, K, d, ldx, lin, c, rule, f, tau, panels_out,
                            inplace)
     fn.last_info = _clip_info(stats, K)
@@ -1309,9 +1236,7 @@ def _clip(fn, wList, rule: int, f, tau, centre, layout, inplace: bool):
         if not panels_in and X is not wList:
             wList.copy_(X)               # (a CPU or non-unit-stride wList was clipped in a copy)
         return wList
-    if isinstance(out, torch.Tensor) and wList.device != out.device:
-        out = out.to(wList.device)
-    return out
+    return _to_caller(out, wList)
 
 
 def clip(wList, tau, centre=None, layout=None, inplace=False):
@@ -1371,74 +1296,54 @@ def clipped(aggregate, tau=None, f=None, layout="panels"):
     Options pass through unchanged (clipping keeps all K rows, so ``honestSize`` stands); the
     caller's dict and wList are not modified.  The result lives on wList.device, as the
     aggregators' own."""
-    if layout not in (None, "rows", "panels"):
-        raise ValueError(f"clipped: layout must be None, 'rows' or 'panels' (got {layout!r})")
+    _panels_out(layout, None, None, "clipped")
     if tau is not None:
         if f is not None:
             raise ValueError("clipped takes tau (static clipping) or f (ARC), not both")
         tau = _clip_tau(tau, "clipped")
 
-    def agg(wList, options={}):  # noqa: B006 - the aggregator contract (M:353)
+    def step(wList, options, name):
         K = int(wList.shape[0])
         centre = options.get("guess") if options else None
-        lay = "rows" if layout == "panels" and K >= 1 and not _has_panels(K) else layout
+        lay = _handover(layout, K)
         if tau is not None:
-            rows = clip(wList, tau, centre=centre, layout=lay)
-        else:
-            f_ = f if f is not None else K - _honest_size(options, agg.__name__)
-            rows = arc(wList, f_, centre=centre, layout=lay)
-        out = aggregate(rows, options)
-        if isinstance(out, torch.Tensor) and out.device != wList.device:
-            out = out.to(wList.device)        # (a CPU wList's clipped rows stayed on the GPU as panels)
-        return out
+            return clip(wList, tau, centre=centre, layout=lay), options
+        f_ = f if f is not None else K - _honest_size(options, name)
+        return arc(wList, f_, centre=centre, layout=lay), options
 
-    agg.__name__ = agg.__qualname__ = f"{aggregate.__name__}_{'arc' if tau is None else 'clip'}"
-    agg.__doc__ = (f"{aggregate.__name__} on the rows clipped about options['guess'] "
-                   f"({'ARC' if tau is None else f'radius {tau}'})")
-    return agg
+    return _pre_step(aggregate, "arc" if tau is None else "clip",
+                     f"{aggregate.__name__} on the rows clipped about options['guess'] "
+                     f"({'ARC' if tau is None else f'radius {tau}'})", step)
 
 
 def honest_variance(w_local, honestSize: int) -> torch.Tensor:
     """getVarience (M:127-129) on the device: the mean over the first honestSize rows
     of ||x_k - mean||^2, one streaming pass (fp64 sums); a 0-dim fp32 tensor."""
     out = torch.empty((), dtype=torch.float32, device=w_local.device)
-    if isinstance(w_local, ClientPanels):
-        _fp32_panels(w_local, "honest_variance")
-        context(w_local.device).call(
-            "gm_honest_variance_panels_f32", w_local.data.data_ptr(), w_local.K, int(honestSize),
-            w_local.d, w_local.panel_stride, out.data_ptr(), _stream_ptr(w_local.device))
-        return out
-    if w_local.device.type != "cuda" or w_local.dtype != torch.float32 or w_local.dim() != 2:
+    if not isinstance(w_local, ClientPanels) and (
+            w_local.device.type != "cuda" or w_local.dtype != torch.float32 or w_local.dim() != 2):
         raise TypeError("honest_variance needs an fp32 CUDA [K, d] matrix or ClientPanels")
-    X, ldx = _unit_rows(w_local)
-    if not 1 <= honestSize <= X.shape[0]:
-        raise ValueError(f"honestSize {honestSize} not in [1, {X.shape[0]}]")
-    context(X.device).call("gm_honest_variance_f32", X.data_ptr(), int(honestSize), X.shape[1],
-                           ldx, out.data_ptr(), _stream_ptr(X.device))
+    X, ldx, layout, K, d = _operand(w_local)
+    if not 1 <= honestSize <= K:
+        raise ValueError(f"honestSize {honestSize} not in [1, {K}]")
+    # (the rows function takes the honest rows alone, its panel twin K as well)
+    rows = (K, int(honestSize)) if layout == _lib.GM_LAYOUT_PANELS else (int(honestSize),)
+    context(X.device).call(_twin("gm_honest_variance_f32", layout), X.data_ptr(), *rows, d, ldx,
+                           out.data_ptr(), _stream_ptr(X.device))
     return out
 
 
 def OMA(message, noise_var=0.01, noise_source=None, seed=None):  # noqa: N802 - reference name
     """In-place per-client equalised AWGN (MNIST_Air_weight.py:385-394)."""
-    if isinstance(message, ClientPanels):
-        _fp32_panels(message, "OMA")
-        src = _noise_source({} if noise_source is None else {"noise_source": noise_source})
-        if src == _lib.GM_NOISE_HOST:          # the reference's [K, d] draws: via rows
-            rows = message.to_rows()
-            OMA(rows, noise_var, noise_source=noise_source, seed=seed)
-            message.copy_rows_(rows)
-            return message
-        context(message.device).call(
-            "gm_oma_philox_panels_f32", message.data.data_ptr(), message.K, message.d,
-            message.panel_stride, float(noise_var), _seed({"seed": seed}),
-            _stream_ptr(message.device))
-        return message
-    if message.dtype != torch.float32:
-        raise TypeError(f"OMA kernel is fp32 (got {message.dtype})")
-    Xc, ldx = _unit_rows(_stage(message))
-    K, d = Xc.shape
-    ctx = context(Xc.device)
+    Xc, ldx, layout, K, d = _operand(message)
     src = _noise_source({} if noise_source is None else {"noise_source": noise_source})
+    panels = isinstance(message, ClientPanels)
+    if panels and src == _lib.GM_NOISE_HOST:   # the reference's [K, d] draws: via rows
+        rows = message.to_rows()
+        OMA(rows, noise_var, noise_source=noise_source, seed=seed)
+        message.copy_rows_(rows)
+        return message
+    ctx = context(Xc.device)
     stream = _stream_ptr(Xc.device)
     if src == _lib.GM_NOISE_HOST:
         sd = math.sqrt(noise_var)
@@ -1450,8 +1355,8 @@ def OMA(message, noise_var=0.01, noise_source=None, seed=None):  # noqa: N802 - 
         ctx.call("gm_oma_apply_f32", Xc.data_ptr(), K, d, ldx, *[t.data_ptr() for t in dev],
                  stream)
     else:
-        ctx.call("gm_oma_philox_f32", Xc.data_ptr(), K, d, ldx, float(noise_var),
+        ctx.call(_twin("gm_oma_philox_f32", layout), Xc.data_ptr(), K, d, ldx, float(noise_var),
                  _seed({"seed": seed}), stream)
-    if Xc is not message:
-        message.copy_(Xc)
+    if not panels and Xc is not message:
+        message.copy_(Xc)                # (a CPU or non-unit-stride message was noised in a copy)
     return message

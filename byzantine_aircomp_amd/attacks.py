@@ -34,8 +34,7 @@ from statistics import NormalDist, StatisticsError
 
 import torch
 
-from . import _lib
-from .aggregators import _stage, _stream_ptr, _unit_rows, context
+from .aggregators import _index, _operand, _shape, _stream_ptr, _with_options, context
 from .panels import ClientPanels, panel_width
 
 __all__ = ["alie", "ipm", "minmax", "minsum", "z_max"]
@@ -58,42 +57,21 @@ def z_max(K: int, B: int) -> float:
         raise ValueError(f"z_max: no z for K = {K}, B = {B}") from None
 
 
-def _sizes(messages, byzantinesize, who: str):
+def _sizes(messages, byzantinesize, who: str, bf16: bool, max_k=None):
     """(K, d, B) after the checks that need no GPU."""
-    if isinstance(messages, ClientPanels):
-        if messages.W != panel_width(messages.K, messages.dtype):
-            raise ValueError(f"{who}: ClientPanels of width {messages.W}, the kernels read "
-                             f"W = {panel_width(messages.K, messages.dtype)} for K = {messages.K} "
-                             f"{messages.dtype} clients")
-    elif not isinstance(messages, torch.Tensor) or messages.dim() != 2:
-        raise ValueError(f"{who}: messages must be a [K, d] tensor or ClientPanels")
-    K, d = (int(n) for n in messages.shape)
-    try:
-        if isinstance(byzantinesize, bool):
-            raise TypeError
-        B = operator.index(byzantinesize)
-    except TypeError:
-        raise ValueError(f"{who}: byzantinesize must be an integer (got {byzantinesize!r})") from None
-    if B < 1 or K - B < 2:
-        raise ValueError(f"{who}: needs 1 <= byzantinesize <= K - 2 (K = {K}, got {B})")
-    return K, d, B
-
-
-def _dtype_check(messages, who: str, bf16_ok: bool):
-    ok = (torch.float32, torch.bfloat16) if bf16_ok else (torch.float32,)
-    if messages.dtype not in ok:
-        raise TypeError(f"{who} works on {' or '.join(str(t) for t in ok)} client updates "
-                        f"(got {messages.dtype})")
+    K, d = _shape(messages, who, bf16=bf16, max_k=max_k)
+    if isinstance(messages, ClientPanels) and messages.W != panel_width(K, messages.dtype):
+        raise ValueError(f"{who}: ClientPanels of width {messages.W}, the kernels read "
+                         f"W = {panel_width(K, messages.dtype)} for K = {K} {messages.dtype} "
+                         "clients")
+    # (at least two honest rows: sigma is their unbiased deviation)
+    return K, d, _index(byzantinesize, who, "byzantinesize", 1, K - 2)
 
 
 def _apply(messages, B: int, call):
     """Run ``call(ctx, X, ldx, layout, stream)`` on the device operand of `messages`, then bring
     the Byzantine rows back where the kernel worked on a copy."""
-    if isinstance(messages, ClientPanels):
-        X, ldx, layout = messages.data, messages.panel_stride, _lib.GM_LAYOUT_PANELS
-    else:
-        X, ldx = _unit_rows(_stage(messages, bf16_ok=True))
-        layout = _lib.GM_LAYOUT_ROWS
+    X, ldx, layout, _, _ = _operand(messages, bf16=True)
     call(context(X.device), X, ldx, layout, _stream_ptr(X.device))
     if not isinstance(messages, ClientPanels) and X is not messages:
         messages[-B:].copy_(X[-B:])
@@ -101,29 +79,15 @@ def _apply(messages, B: int, call):
 
 
 def _affine(messages, byzantinesize, who: str, a: float, b: float):
-    _dtype_check(messages, who, bf16_ok=True)
-    K, d, B = _sizes(messages, byzantinesize, who)
+    K, d, B = _sizes(messages, byzantinesize, who, True)
     fn = "gm_attack_affine_bf16" if messages.dtype == torch.bfloat16 else "gm_attack_affine_f32"
     return _apply(messages, B, lambda ctx, X, ldx, layout, stream: ctx.call(
         fn, X.data_ptr(), K, d, ldx, layout, B, float(a), float(b), stream))
 
 
-def _named(fn, name: str, doc: str):
-    fn.__name__ = fn.__qualname__ = name
-    fn.__doc__ = doc
-    return fn
-
-
-def _only(who: str, given: dict, *names):
-    unknown = sorted(set(given) - set(names))
-    if unknown:
-        raise TypeError(f"{who}.with_options takes {', '.join(names)} (got {unknown})")
-
-
 def _run_alie(messages, byzantinesize, z=None):
     if z is None:
-        _dtype_check(messages, "alie", bf16_ok=True)
-        K, _, B = _sizes(messages, byzantinesize, "alie")
+        K, _, B = _sizes(messages, byzantinesize, "alie", True)
         z = z_max(K, B)
     alie.last_z = float(z)
     return _affine(messages, byzantinesize, "alie", 1.0, -float(z))
@@ -138,17 +102,14 @@ def alie(messages, byzantinesize):
     return _run_alie(messages, byzantinesize)
 
 
-def _alie_with_options(**fixed):
-    """An ``attack(messages, byzantinesize)`` named "alie" with a fixed z."""
-    _only("alie", fixed, "z")
-    z = fixed.get("z")
-    if z is not None:
-        z = float(z)
-    return _named(lambda messages, byzantinesize: _run_alie(messages, byzantinesize, z), "alie",
-                  f"alie with {fixed}")
+def _alie_fixed(fixed):
+    z = None if fixed.get("z") is None else float(fixed["z"])
+    return lambda messages, byzantinesize: _run_alie(messages, byzantinesize, z)
 
 
-alie.with_options = _alie_with_options
+alie.with_options = _with_options(
+    "alie", ("z",), _alie_fixed,
+    """An ``attack(messages, byzantinesize)`` named "alie" with a fixed z.""")
 alie.last_z = None
 
 
@@ -163,46 +124,41 @@ def ipm(messages, byzantinesize):
     return _run_ipm(messages, byzantinesize)
 
 
-def _ipm_with_options(**fixed):
-    """An ``attack(messages, byzantinesize)`` named "ipm" with a fixed epsilon."""
-    _only("ipm", fixed, "epsilon")
+def _ipm_fixed(fixed):
     eps = float(fixed.get("epsilon", 0.1))
-    return _named(lambda messages, byzantinesize: _run_ipm(messages, byzantinesize, eps), "ipm",
-                  f"ipm with {fixed}")
+    return lambda messages, byzantinesize: _run_ipm(messages, byzantinesize, eps)
 
 
-ipm.with_options = _ipm_with_options
+ipm.with_options = _with_options(
+    "ipm", ("epsilon",), _ipm_fixed,
+    """An ``attack(messages, byzantinesize)`` named "ipm" with a fixed epsilon.""")
+
+
+def _dev(who: str, dev) -> int:
+    if dev not in _DEVS:
+        raise ValueError(f"{who}: dev must be one of {', '.join(_DEVS)} (got {dev!r})")
+    return _DEVS[dev]
 
 
 def _run_minmax(base, rule: int, messages, byzantinesize, dev="std"):
     who = base.__name__
-    if dev not in _DEVS:
-        raise ValueError(f"{who}: dev must be one of {', '.join(_DEVS)} (got {dev!r})")
-    _dtype_check(messages, who, bf16_ok=False)
-    K, d, B = _sizes(messages, byzantinesize, who)
-    if K > 4096:
-        raise ValueError(f"{who}: K <= 4096 (got {K})")
+    dev = _dev(who, dev)
+    K, d, B = _sizes(messages, byzantinesize, who, False, 4096)
     gamma = C.c_double(0.0)
     out = _apply(messages, B, lambda ctx, X, ldx, layout, stream: ctx.call(
-        "gm_attack_minmax_f32", X.data_ptr(), K, d, ldx, layout, B, rule, _DEVS[dev],
+        "gm_attack_minmax_f32", X.data_ptr(), K, d, ldx, layout, B, rule, dev,
         C.byref(gamma), stream))
     base.last_gamma = gamma.value
     return out
 
 
-def _minmax_with_options(base, rule: int):
-    def with_options(**fixed):
-        _only(base.__name__, fixed, "dev")
+def _minmax_fixed(base, rule: int):
+    def make(fixed):
         dev = fixed.get("dev", "std")
-        if dev not in _DEVS:
-            raise ValueError(f"{base.__name__}: dev must be one of {', '.join(_DEVS)} "
-                             f"(got {dev!r})")
-        return _named(lambda messages, byzantinesize: _run_minmax(base, rule, messages,
-                                                                  byzantinesize, dev),
-                      base.__name__, f"{base.__name__} with {fixed}")
-    with_options.__doc__ = (f'An ``attack(messages, byzantinesize)`` named "{base.__name__}" with '
-                            'a fixed deviation ("std", "unit" or "sign").')
-    return with_options
+        _dev(base.__name__, dev)
+        return lambda messages, byzantinesize: _run_minmax(base, rule, messages, byzantinesize,
+                                                           dev)
+    return make
 
 
 def minmax(messages, byzantinesize):
@@ -222,6 +178,9 @@ def minsum(messages, byzantinesize):
     return _run_minmax(minsum, 1, messages, byzantinesize)
 
 
-minmax.with_options = _minmax_with_options(minmax, 0)
-minsum.with_options = _minmax_with_options(minsum, 1)
+for _base, _rule in ((minmax, 0), (minsum, 1)):
+    _base.with_options = _with_options(
+        _base.__name__, ("dev",), _minmax_fixed(_base, _rule),
+        f'An ``attack(messages, byzantinesize)`` named "{_base.__name__}" with a fixed deviation '
+        '("std", "unit" or "sign").')
 minmax.last_gamma = minsum.last_gamma = None

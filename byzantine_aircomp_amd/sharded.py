@@ -23,10 +23,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .aggregators import (GMResult, Context, _cclip_params, _clip_centre, _clip_info, _clip_shape,
-                          _clip_tau, _fltrust_info, _fltrust_server, _fltrust_shape, _fltrust_vec,
-                          _gm_opts, _nnm_f, _noise_source, _result, _run_cclip, _run_clip,
-                          _run_fltrust, _stream_ptr)
+from .aggregators import (GMResult, Context, _cclip_params, _clip_args, _clip_info,
+                          _fltrust_args, _fltrust_info, _gm_opts, _noise_source, _operand, _result,
+                          _run_cclip, _run_clip, _run_fltrust, _stream_ptr, _vector)
 from .panels import ClientPanels
 
 __all__ = ["shard_range", "ShardedGM", "torch_allreduce_adapter"]
@@ -145,12 +144,8 @@ class ShardedGM:
         opts = {"maxiter": 200, "tol": 1e-5, "noise_var": None, "P_max": 1}
         opts.update(options or {})
         opts["check_every"] = 0            # (not an option of the sharded calls)
-        X_in = X
-        X, ptr, ldx, layout = self._operand(X)
-        guess = opts.get("guess")
-        if guess is None:
-            raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
-        g0 = guess.to(device=self.device, dtype=torch.float32).contiguous()
+        data, ldx, layout, K = self._operand(X)
+        g0 = self._guess(opts)
         out = torch.empty(self.d_local, dtype=torch.float32, device=self.device)
         pre_var = None if aircomp else opts.get("pre_oma_var")
         # OMA pre-noise on this rank's columns (keyed by global column: the shards
@@ -165,25 +160,37 @@ class ShardedGM:
                 raise ValueError("sharded AirComp needs options['seed'] identical on every rank")
         o = _gm_opts(opts, aircomp, layout, pre_var, opts.get("pre_oma_seed"))
         res = _lib.GmResult()
-        self.ctx.call("gm_weiszfeld_f32", ptr, X.shape[0], self.d_local, ldx, g0.data_ptr(),
+        self.ctx.call("gm_weiszfeld_f32", data.data_ptr(), K, self.d_local, ldx, g0.data_ptr(),
                       out.data_ptr(), C.byref(o), C.byref(res), _stream_ptr(self.device))
         self.last_result = _result(res, self.ctx)
-        if o.pre_oma and X is not X_in:
-            X_in.copy_(X)      # the fused pre-noise is in place on the caller's shard
+        if o.pre_oma and not isinstance(X, ClientPanels) and data is not X:
+            X.copy_(data)      # the fused pre-noise is in place on the caller's shard
         return out
 
     def _operand(self, X):
-        """(X to keep alive, pointer, ldx, layout) of this rank's fp32 [K, d_local] columns,
-        as rows or as a ClientPanels."""
-        if X.shape[1] != self.d_local or X.device != self.device or X.dtype != torch.float32:
-            raise ValueError(f"X must be fp32 [K, {self.d_local}] on {self.device}")
-        if isinstance(X, ClientPanels):
-            return X, X.data.data_ptr(), X.panel_stride, _lib.GM_LAYOUT_PANELS
-        if X.stride(1) != 1 or X.data_ptr() % 16 or (X.stride(0) % 4 and X.shape[0] > 1):
+        """(tensor, ldx, layout, K) of this rank's fp32 [K, d_local] columns, rows or a
+        ClientPanels: aggregators._operand under this class's stricter rule (the exact device
+        and width, nothing staged)."""
+        self._check(X)
+        if not isinstance(X, ClientPanels) and (
+                X.stride(1) != 1 or X.data_ptr() % 16 or (X.stride(0) % 4 and X.shape[0] > 1)):
             # unit stride and float4-aligned rows, as on every other rank: the AUTO
             # Gram decision is global, so a rank must never fall short of it locally
             X = X.clone(memory_format=torch.contiguous_format)
-        return X, X.data_ptr(), max(X.stride(0), self.d_local), _lib.GM_LAYOUT_ROWS
+        return _operand(X)[:4]
+
+    def _check(self, X, width_only=False):
+        """X is this rank's shard.  width_only: ahead of the argument checks, so that a vector's
+        length is held against d_local; the dtype is then theirs to refuse (TypeError)."""
+        if X.shape[1] != self.d_local or not (width_only or (X.device == self.device
+                                                             and X.dtype == torch.float32)):
+            raise ValueError(f"X must be fp32 [K, {self.d_local}] on {self.device}")
+
+    def _guess(self, options):
+        """options['guess'], this rank's shard of the starting point, as the library reads it."""
+        if options.get("guess") is None:
+            raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
+        return _vector(options["guess"], self.d_local, self.device, "guess")
 
     def cclip(self, X, options):
         """Centered clipping (aggregators.cclip) on this rank's [K, d_local] columns, fp32 rows
@@ -194,15 +201,10 @@ class ShardedGM:
         ``last_clipped`` the clients outside the radius at the last iteration run."""
         options = options or {}
         params = _cclip_params(options)
-        guess = options.get("guess")
-        if guess is None:
-            raise ValueError("sharded aggregation needs options['guess'] (this rank's shard)")
-        X, ptr, ldx, layout = self._operand(X)
-        g0 = guess.to(device=self.device, dtype=torch.float32).contiguous()
-        if g0.numel() != self.d_local:
-            raise ValueError(f"guess has {g0.numel()} elements, this shard has {self.d_local}")
+        g0 = self._guess(options)
+        data, ldx, layout, K = self._operand(X)
         out, self.last_result, self.last_clipped = _run_cclip(
-            self.ctx, ptr, False, X.shape[0], self.d_local, ldx, layout, g0, params)
+            self.ctx, data.data_ptr(), False, K, self.d_local, ldx, layout, g0, params)
         return out
 
     def fltrust(self, X, options):
@@ -211,37 +213,23 @@ class ShardedGM:
         ``server_row`` a row of X, identical on every rank.  The 2K + 1 fp64 sums are
         all-reduced once; every rank derives the same trust scores and coefficients
         (``last_info``, as ``fltrust.last_info``, holds the same bits on every rank)."""
-        options = options or {}
-        K, _ = _fltrust_shape(X, "ShardedGM.fltrust")
-        if X.dtype != torch.float32:
-            raise TypeError(f"ShardedGM.fltrust reads fp32 shards (got {X.dtype})")
-        su, row = _fltrust_server(options, K, self.d_local)
-        guess = options.get("guess")
-        if guess is not None and guess.numel() != self.d_local:
-            raise ValueError(f"guess has {guess.numel()} elements, this shard has {self.d_local}")
-        X, ptr, ldx, layout = self._operand(X)
-        data = X.data if isinstance(X, ClientPanels) else X
-        server = _fltrust_vec(su, self.d_local, self.device, "server_update")
-        centre = _fltrust_vec(guess, self.d_local, self.device, "guess")
+        self._check(X, width_only=True)
+        K, _, su, row, guess = _fltrust_args(X, options, "ShardedGM.fltrust", bf16=False)
+        data, ldx, layout, K = self._operand(X)
+        server = _vector(su, self.d_local, self.device, "server_update")
+        centre = _vector(guess, self.d_local, self.device, "guess")
         out, stats = _run_fltrust(self.ctx, data, K, self.d_local, ldx, layout, server, row,
                                   centre)
         self.last_info = _fltrust_info(stats, K)
         return out
 
     def _clip(self, who, X, rule, f, tau, centre):
-        K, _ = _clip_shape(X, who)
-        if X.dtype != torch.float32:
-            raise TypeError(f"{who} reads fp32 shards (got {X.dtype})")
-        if rule == _lib.GM_CLIP_ARC:
-            f, tau = _nnm_f(f, K, who), 0.0
-        else:
-            f, tau = 0, _clip_tau(tau, who)
-        centre = _clip_centre(centre, self.d_local, who)
-        X, ptr, ldx, layout = self._operand(X)
-        panels = isinstance(X, ClientPanels)
-        out, stats = _run_clip(self.ctx, X.data if panels else X, K, self.d_local, ldx, layout,
-                               _fltrust_vec(centre, self.d_local, self.device, "centre"), rule, f,
-                               tau, panels)
+        self._check(X, width_only=True)
+        K, _, f, tau, centre = _clip_args(X, who, rule, f, tau, centre, bf16=False)
+        data, ldx, layout, K = self._operand(X)
+        out, stats = _run_clip(self.ctx, data, K, self.d_local, ldx, layout,
+                               _vector(centre, self.d_local, self.device, "centre"), rule, f,
+                               tau, isinstance(X, ClientPanels))
         self.last_info = _clip_info(stats, K)
         return out
 

@@ -284,6 +284,17 @@ class _ClientChain:
         later draws touch only its own generator)."""
         return torch.tensor([s._next_index() for s in streams], dtype=torch.int32)
 
+    @staticmethod
+    def _written(M):
+        """(tensor, ld, layout) of the client matrix a kernel writes in place: a device-resident
+        [K, d] tensor or ClientPanels as they are (a copy would take the writes)."""
+        from .aggregators import _operand
+        from .panels import ClientPanels
+        buf, ld, lay, _, _ = _operand(M)
+        if not isinstance(M, ClientPanels) and buf is not M:
+            raise RuntimeError("the client matrix must be on the GPU with unit column stride")
+        return buf, ld, lay
+
     def step(self, local, clients, honest, attack_name, gamma, wd):
         from . import _lib
         from .aggregators import _stream_ptr
@@ -294,11 +305,7 @@ class _ClientChain:
         Wt, bt = self.lin.weight, self.lin.bias
         if not (Wt.is_contiguous() and bt.is_contiguous()):
             raise RuntimeError("the model's weight and bias must be contiguous")
-        X = clients.X
-        if clients.layout == "panels":
-            buf, ldx, lay = X.data, X.panel_stride, _lib.GM_LAYOUT_PANELS
-        else:
-            buf, ldx, lay = X, X.stride(0), _lib.GM_LAYOUT_ROWS
+        buf, ldx, lay = self._written(clients.X)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gm_client_chain_f32(
                 self.ctx.handle, self.x.data_ptr(), self.F, self.y.data_ptr(), self.F, self.C,
@@ -312,7 +319,6 @@ class _ClientChain:
         one launch of gm_client_grads_f32 (client_grads.hip), one workgroup per client."""
         from . import _lib
         from .aggregators import _stream_ptr
-        from .panels import ClientPanels
         K = local.shape[0] if local.dim() == 2 else -1
         if local.shape != (K, self.B):
             raise RuntimeError("client batches must be full batches of batchSize samples")
@@ -320,10 +326,7 @@ class _ClientChain:
         Wt, bt = self.lin.weight, self.lin.bias
         if not (Wt.is_contiguous() and bt.is_contiguous()):
             raise RuntimeError("the model's weight and bias must be contiguous")
-        if isinstance(M, ClientPanels):
-            buf, ldx, lay = M.data, M.panel_stride, _lib.GM_LAYOUT_PANELS
-        else:
-            buf, ldx, lay = M, M.stride(0), _lib.GM_LAYOUT_ROWS
+        buf, ldx, lay = self._written(M)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gm_client_grads_f32(
                 self.ctx.handle, self.x.data_ptr(), self.F, self.y.data_ptr(), self.F, self.C,
