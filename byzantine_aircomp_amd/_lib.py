@@ -112,6 +112,9 @@ SIGNATURES = [
     ("gm_median_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     ("gm_trimmed_mean_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     ("gm_krum_panels_f32", C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, C.POINTER(_I64), _P]),
+    ("gm_mean_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _P]),
+    ("gm_median_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _P]),
+    ("gm_trimmed_mean_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _P, _P]),
     ("gm_krum_last_info", C.c_int, [_P, C.POINTER(_I64)]),
     ("gm_delta_last_info", C.c_int, [_P, C.POINTER(_I64)]),
     ("gm_meamed_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _I64, _P, _P]),

@@ -642,27 +642,67 @@ cclip.with_options = _with_options(
 cclip.last_info = {"clipped": 0}
 
 
-def _coordinate(wList, fn_name, *extra):
-    X, ldx, layout, K, d = _operand(wList)
+def _coordinate(wList, options, fn_name, *extra):
+    """mean / median / trimmed_mean: the fp32 function `fn_name` (its panel twin on fp32
+    ClientPanels).  With ``options["bf16"]`` true, bf16 input goes to the ``_bf16`` counterpart,
+    which takes the layout as an argument and reads unit-stride rows in place at any alignment;
+    without it bf16 is refused as every other 16- or 64-bit dtype is (the call is fp32 unless
+    the caller says otherwise).  The dtype is checked before anything is staged."""
+    dtype = wList.data.dtype if isinstance(wList, ClientPanels) else wList.dtype
+    bf16 = dtype == torch.bfloat16
+    if bf16 and not (options and options.get("bf16")):
+        raise TypeError("aggregation kernels are fp32 (got torch.bfloat16; options={'bf16': "
+                        "True} reads bf16 client updates in place)")
+    if dtype != torch.float32 and not bf16:
+        raise TypeError(f"aggregation kernels read fp32 or bf16 client updates (got {dtype})")
+    X, ldx, layout, K, d = _operand(wList, bf16=bf16)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
-    context(X.device).call(_twin(fn_name, layout), X.data_ptr(), K, d, ldx, *extra,
-                           out.data_ptr(), _stream_ptr(X.device))
+    if bf16:
+        context(X.device).call(fn_name.replace("_f32", "_bf16"), X.data_ptr(), K, d, ldx, layout,
+                               *extra, out.data_ptr(), _stream_ptr(X.device))
+    else:
+        context(X.device).call(_twin(fn_name, layout), X.data_ptr(), K, d, ldx, *extra,
+                               out.data_ptr(), _stream_ptr(X.device))
     return _to_caller(out, wList)
 
 
+_BF16_INPUT = """wList: an fp32 [K, d] tensor (any stride; a CPU tensor is staged to the GPU) or
+    fp32 ClientPanels; never written.  With ``options={"bf16": True}`` also a bf16 [K, d] tensor in
+    any form (a unit-stride CUDA tensor is read in place at any alignment) or bf16 ClientPanels:
+    the values are widened (exact) and the result is the fp32 call's on ``wList.float()``.
+    Without the option bf16 raises TypeError, as fp16 / fp64 always do, before a GPU is
+    touched.  The result is fp32 [d] on wList's device."""
+
+
 def mean(wList, options={}):  # noqa: B006 - reference signature (M:186)
-    """Column mean (MNIST_Air_weight.py:186-187)."""
-    return _coordinate(wList, "gm_mean_f32")
+    return _coordinate(wList, options, "gm_mean_f32")
+
+
+mean.__doc__ = f"""Column mean (MNIST_Air_weight.py:186-187): an fp64 sum per column, rounded once.
+
+    {_BF16_INPUT}"""
 
 
 def median(wList, options={}):  # noqa: B006 - reference signature (M:194)
-    """Coordinate-wise lower median, torch.median semantics (M:194-195)."""
-    return _coordinate(wList, "gm_median_f32")
+    return _coordinate(wList, options, "gm_median_f32")
+
+
+median.__doc__ = f"""Coordinate-wise lower median, torch.median semantics (M:194-195), K <= 2048:
+    the element of rank (K - 1) // 2, NaN for a column that holds one (on bf16: 16-bit order keys,
+    half the counting steps).
+
+    {_BF16_INPUT}"""
 
 
 def trimmed_mean(wList, options={}):  # noqa: B006 - reference signature (M:189)
-    """Coordinate-wise mean without the int(0.1 K) smallest and largest (M:189-192)."""
-    return _coordinate(wList, "gm_trimmed_mean_f32", int(wList.shape[0] * 0.1))
+    return _coordinate(wList, options, "gm_trimmed_mean_f32", int(wList.shape[0] * 0.1))
+
+
+trimmed_mean.__doc__ = f"""Coordinate-wise mean without the int(0.1 K) smallest and largest
+    (M:189-192), K <= 2048: the kept values summed in fp64 and rounded once (on bf16 they are
+    selected on 16-bit order keys).
+
+    {_BF16_INPUT}"""
 
 
 def Krum(wList, options):  # noqa: N802 - reference name (M:197)

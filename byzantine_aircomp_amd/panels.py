@@ -16,10 +16,13 @@ the 32-wave rows kernel; equal to rounding otherwise.
 
 ``ClientPanels(..., dtype=torch.bfloat16)`` stores the values as bf16 in the layout of
 ``gm_weiszfeld_bf16`` (W = ``gm_panel_width_bf16(K)``): half the bytes per streaming pass.
-``gm2`` / ``gm`` / ``cclip`` read them widened to fp32 (exact) and return fp32; the other
-aggregators take fp32 panels only.  ``bucketing`` (s-bucketing, aggregators.py) reads fp32 and
-bf16 panels alike and writes its fp32 bucket means as ``ClientPanels(ceil(K/s), d)``, whose
-panel width is that of the smaller K.
+``gm2`` / ``gm`` / ``cclip`` read them widened to fp32 (exact) and return fp32, and so do
+``fltrust``, ``clip`` / ``arc``, the attacks and, under ``options={"bf16": True}``, ``mean`` /
+``median`` / ``trimmed_mean`` (coordinate_bf16.hip: the selections on 16-bit order keys; without
+the option those three stay fp32 and raise on bf16); ``Krum``, ``meamed``, ``multi_krum``,
+``bulyan``, ``nnm`` and ``dnc`` take fp32 panels only.  ``bucketing`` (s-bucketing,
+aggregators.py) reads fp32 and bf16 panels alike and writes its fp32 bucket means as
+``ClientPanels(ceil(K/s), d)``, whose panel width is that of the smaller K.
 """
 from __future__ import annotations
 

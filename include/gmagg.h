@@ -310,6 +310,24 @@ int gm_trimmed_mean_panels_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d
                                int64_t panel_stride, int64_t trim, float* out, void* stream);
 int gm_krum_panels_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t panel_stride,
                        int64_t honest_size, float* out, int64_t* index, void* stream);
+/* mean, median and trimmed mean of bf16 client updates (coordinate_bf16.hip): X holds bfloat16
+ * bit patterns, layout GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any 2-byte alignment; 16-byte loads
+ * where the base is 16-byte aligned and ldx % 8 == 0) or GM_LAYOUT_PANELS ([ceil(d/W)][K][W],
+ * W = gm_panel_width_bf16(K), ldx = panel stride >= K*W).  X is never written; out[d] is fp32.
+ * The results are the fp32 functions' definitions on the widened values (exact): the median is
+ * the widened element of rank (K-1)/2 (NaN for a column that holds a NaN), the mean and the
+ * trimmed mean (0 <= 2 trim <= K-1) are fp64 sums rounded once, and both layouts and every
+ * alignment return the same bits.  The selections work on 16-bit order keys: at most 16
+ * counting steps per rank, or two 256-bin histograms.  GM_ERR_INVALID: a NULL argument, K < 1, d < 0, an unknown layout,
+ * ldx < d on rows, a panel stride < K*W, trim out of range.  GM_ERR_UNSUPPORTED: K > 2048 for
+ * the median and the trimmed mean (the mean has no limit on rows), or panels at a K without a
+ * bf16 panel width.  A refused call writes nothing. */
+int gm_mean_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                 int32_t layout, float* out, void* stream);
+int gm_median_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                   int32_t layout, float* out, void* stream);
+int gm_trimmed_mean_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout, int64_t trim, float* out, void* stream);
 
 /* Krum's algorithm (round 5).  K <= 256 on large inputs (AUTO: K >= 64 and K^2 d >= 2^29;
  * env GMAGG_KRUM=0 exact only, 1 Gram wherever eligible): the scaled-f16 Gram MFMA kernel
