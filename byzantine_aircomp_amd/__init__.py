@@ -8,9 +8,9 @@ HIP kernels for gfx950 behind a C ABI (include/gmagg.h, libgmagg.so):
 See DESIGN.md for the kernels and INTEGRATION.md for swapping them into the
 reference's training loop.
 """
-from .aggregators import (GMResult, Krum, OMA, arc, bucketed, bucketing, bulyan, cclip,  # noqa: F401
-                          clip, clipped, context, dnc, fltrust, gm, gm2, meamed, mean, median, mixed,
-                          multi_krum, nnm, trimmed_mean)
+from .aggregators import (GMResult, Krum, OMA, arc, bucketed, bucketing, bulyan, caf,  # noqa: F401
+                          cclip, clip, clipped, context, dnc, fltrust, gm, gm2, meamed, mean, median,
+                          mixed, multi_krum, nnm, trimmed_mean)
 from .attacks import alie, ipm, minmax, minsum, z_max  # noqa: F401
 from .panels import ClientPanels, panel_width  # noqa: F401
 

@@ -125,6 +125,11 @@ SIGNATURES = [
     ("gm_dnc_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _I64, _I64, _I64,
                              C.c_double, _P, _P, C.POINTER(C.c_int32), C.POINTER(_I64),
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    ("gm_caf_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _I64, C.c_double, _P, _P,
+                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                             _P]),
+    ("gm_weighted_mean_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _P, _P]),
     ("gm_fltrust_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
     ("gm_fltrust_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _P, _P, _P, _P]),
     ("gm_clip_rows_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, C.c_int32, _I64,

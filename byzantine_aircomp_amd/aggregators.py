@@ -57,6 +57,11 @@ sample's top singular vector are largest are dropped (``int(dnc_c * f)`` per rou
 rounds) and the rest averaged; fp32 rows or panels and ``honestSize`` like ``Krum``;
 ``dnc.with_options(...)`` fixes its options; it works under ``bucketed`` and ``mixed`` and as a
 training loop's ``aggregate``.
+``caf(wList, options)`` is the covariance filter (Diakonikolas et al., ICML 2017; ByzFL's CAF):
+the rows that stand out along the top eigen-direction of the weighted covariance of all d
+coordinates are weighted down round by round, in fp64 on the K x K squared distances, and the
+weighted mean of the round with the smallest eigenvalue is returned; fp32 rows or panels and
+``honestSize`` like ``Krum``; ``caf.with_options(...)`` fixes its options.
 ``fltrust(wList, options)`` is FLTrust (Cao, Fang, Liu & Gong, NDSS 2021): every row is scored by
 the cosine of its update with the server's own (``server_update``, or row ``server_row``), and
 the rows of positive score, rescaled to the server update's norm, are averaged with their scores
@@ -85,7 +90,7 @@ from .panels import ClientPanels
 
 __all__ = ["gm2", "gm", "cclip", "OMA", "mean", "median", "trimmed_mean", "Krum", "GMResult",
            "last_result", "Context", "context", "honest_variance", "bucketing", "bucketed",
-           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc", "fltrust", "clip", "arc",
+           "multi_krum", "bulyan", "meamed", "nnm", "mixed", "dnc", "caf", "fltrust", "clip", "arc",
            "clipped"]
 
 
@@ -1094,6 +1099,82 @@ dnc.with_options = _with_options(
     over the caller's, for loops that build the dict themselves
     (training.run(..., aggregate=dnc.with_options(dnc_c=1.5, dnc_iters=3))).""")
 dnc.last_columns = dnc.last_selected = dnc.last_scores = dnc.last_info = None
+
+
+_CAF_KEYS = ("power_iters", "power_tol")
+
+
+def _caf_scalars(options):
+    """(power_iters, power_tol) of a caf options dict, refused with ValueError where out of
+    range."""
+    pit = int(options.get("power_iters", 100))
+    if pit < 1:
+        raise ValueError(f"caf: power_iters must be >= 1 (got {options.get('power_iters')!r})")
+    ptol = float(options.get("power_tol", 1e-10))
+    if not ptol >= 0:
+        raise ValueError(f"caf: power_tol must be >= 0 (got {options.get('power_tol')!r})")
+    return pit, ptol
+
+
+def caf(wList, options):
+    """CAF, the covariance filter (the down-weighting filter of Diakonikolas et al., "Being Robust
+    (in High Dimensions) Can Be Practical", ICML 2017; ByzFL's Covariance-bound Agnostic Filter):
+    while the weights c (all 1 at first) sum to more than K - 2f, f = K - honestSize, find the top
+    eigenpair of the weighted covariance of all d coordinates by power iteration, remember the
+    weights of the round with the smallest eigenvalue, and scale every weight down by its row's
+    squared projection on the eigenvector over the largest one (that row's weight becomes 0).
+    The result is the mean weighted by the remembered c*.  All of it in fp64 on the GPU, solved on
+    the K x K squared distances without ever forming the covariance (gm_caf_f32, caf.hip);
+    include/gmagg.h has the definition, start vector and tie rules.  Bit-identical for rows, panels
+    and every alignment; f == 0 is ``mean``.  Where ``dnc`` filters on sampled columns, this sees
+    every coordinate.  A non-finite entry ends the filter with all weights 1: compose with
+    ``clipped`` / ``arc`` for that.
+
+    wList: an fp32 [K, d] tensor (any stride; a CPU tensor is staged and the result copied back)
+    or fp32 ClientPanels, 2 <= K <= 4096; never written.  bf16, fp64 (TypeError), a missing
+    ``honestSize``, 2f >= K, K < 2, power_iters < 1 (ValueError) are refused before a GPU is
+    touched.  Options: ``honestSize`` (required), ``power_iters`` (100) and ``power_tol`` (1e-10),
+    the iteration's cap per round and its stop on the unit iterate's movement.  Every other key is
+    ignored.
+
+    After a call ``caf.last_weights`` holds the fp64 [K] c* on the GPU and ``caf.last_info``
+    ``{"rounds", "best_round", "eigenvalue", "weight", "power_iters": [...], "converged": [...]}``:
+    the rounds run, the round whose weights were kept, its eigenvalue, S* = sum c*, and per round
+    the applications run and whether the movement test passed."""
+    K, d = _shape(wList, "caf", max_k=4096)
+    honest = _honest_size(options, "caf")
+    pit, ptol = _caf_scalars(options)
+    f = K - honest
+    if K < 2:
+        raise ValueError(f"caf: K >= 2 (got {K})")
+    if honest < 1 or f < 0:
+        raise ValueError(f"caf: honestSize {honest} not in [1, {K}]")
+    if 2 * f >= K:
+        raise ValueError(f"caf: 2f = 2 * {f} >= K = {K}: needs an honest majority")
+    X, ldx, layout, K, d = _operand(wList)
+    out = torch.empty(d, dtype=torch.float32, device=X.device)
+    weights = torch.ones(K, dtype=torch.float64, device=X.device)
+    lam, S = C.c_double(math.nan), C.c_double(float(K))
+    rounds, best = C.c_int32(0), C.c_int32(0)
+    nit, conv = (C.c_int32 * K)(), (C.c_int32 * K)()
+    if d > 0:
+        context(X.device).call("gm_caf_f32", X.data_ptr(), K, d, ldx, layout, f, pit, ptol,
+                               out.data_ptr(), weights.data_ptr(), C.byref(lam), C.byref(S),
+                               C.byref(rounds), C.byref(best), nit, conv, _stream_ptr(X.device))
+    n = rounds.value
+    caf.last_weights = weights
+    caf.last_info = {"rounds": n, "best_round": best.value, "eigenvalue": lam.value,
+                     "weight": S.value, "power_iters": list(nit[:n]),
+                     "converged": [bool(x) for x in conv[:n]]}
+    return _to_caller(out, wList)
+
+
+caf.with_options = _with_options(
+    "caf", _CAF_KEYS, _fixed_options("caf", _caf_scalars),
+    """An ``aggregate(wList, options)`` callable named "caf" that applies the given caf options
+    over the caller's, for loops that build the dict themselves
+    (training.run(..., aggregate=caf.with_options(power_iters=50))).""")
+caf.last_weights = caf.last_info = None
 
 
 _FLTRUST_KEYS = ("server_update", "server_row")

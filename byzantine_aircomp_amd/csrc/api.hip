@@ -1,5 +1,6 @@
 // C ABI of libgmagg.so (include/gmagg.h): contexts, the coordinate-wise aggregators, Krum's
-// host side, MeaMed / Multi-Krum / Bulyan, nearest-neighbor mixing, OMA, the synthetic fills,
+// host side, MeaMed / Multi-Krum / Bulyan, nearest-neighbor mixing, DnC's and the covariance
+// filter's host loops, OMA, the synthetic fills,
 // the panel pack, s-bucketing,
 // the omniscient attacks and the client chain.  The Weiszfeld
 // entry points are in host_weiszfeld.hip and host_batched.hip; what the three share is in
@@ -639,6 +640,114 @@ int gm_dnc_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int
   *n_good = m;                                       // >= K - remove * iters >= 1
   if (stop == 2) return GM_OK;
   HIPCHK(launch_gather_mean(X, d, ldx, ws, list, m, out, s));
+  return GM_OK;
+}
+
+// GMAGG_CAF_STOP (read per call; tools/caf_bench.py times the stages apart with it): 1 returns
+// after the distances, 2 after the last round (before the weighted mean); anything else runs the
+// whole call.
+static int caf_stop() { return env_int("GMAGG_CAF_STOP", 0); }
+
+int gm_caf_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+               int64_t f, int64_t power_iters, double power_tol, float* out, double* weights,
+               double* eigenvalue, double* weight, int32_t* rounds, int32_t* best_round,
+               int32_t* niter, int32_t* converged, void* stream) {
+  if (!c || !X || !out) return fail(GM_ERR_INVALID, "gm_caf_f32: a NULL ctx, X or out");
+  if (K < 2 || d < 0 || !known_layout(layout) || f < 0 || 2 * f >= K || power_iters < 1 ||
+      !(power_tol >= 0))
+    return fail(GM_ERR_INVALID, "gm_caf_f32: bad args (K < 2, d < 0, an unknown layout, f < 0, "
+                "2f >= K, power_iters < 1, power_tol not >= 0)");
+  if (K > 4096) return fail(GM_ERR_UNSUPPORTED, "gm_caf_f32: K <= 4096 (got %lld)", (long long)K);
+  int ws = 0;
+  int rc = robust_shift("gm_caf_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (c->d_total > 0 || c->comm || c->ar_fn)
+    return fail(GM_ERR_UNSUPPORTED, "gm_caf_f32: a d-sharded or collective context (the distances "
+                "would need a K x K all-reduce)");
+  if (d == 0) return GM_OK;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  CafWork cw{};
+  const size_t need = caf_layout(nullptr, K, &cw);
+  const double nan = std::nan("");
+  if (f == 0) {            // no round runs: the column mean, gm_mean_f32's launch, and c* = 1
+    HIPCHK(launch_col_mean(X, K, d, ldx, out, s, ws));
+    if (weights) {
+      rc = grow_ws(c, need);
+      if (rc) return rc;
+      caf_layout(c->ws, K, &cw);
+      HIPCHK(launch_caf_begin(cw, K, 0, s));
+      HIPCHK(hipMemcpyAsync(weights, cw.c, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, s));
+    }
+    if (eigenvalue) *eigenvalue = nan;
+    if (weight) *weight = (double)K;
+    if (rounds) *rounds = 0;
+    if (best_round) *best_round = 0;
+    return GM_OK;
+  }
+  // Krum's workspace (D in the G area, the slices' partials in the float slab); the partials
+  // are dead once D is reduced, and the slab then holds the solver's O(K) state
+  const size_t part_doubles = (size_t)krum_slices(K, d) * (size_t)(K * K);
+  Workspace w;
+  rc = ensure_ws(c, K, 1, 1, &w, std::max(2 * part_doubles, (need + 3) / 4), (int)K);
+  if (rc) return rc;
+  rc = ensure_host(c, sizeof(CafState));
+  if (rc) return rc;
+  HIPCHK(launch_krum_dist(X, K, d, ldx, ws, w.G, reinterpret_cast<double*>(w.gslab), s));
+  const int stop = caf_stop();
+  if (stop == 1) return GM_OK;
+  caf_layout(reinterpret_cast<char*>(w.gslab), K, &cw);
+  cw.D = w.G;
+  HIPCHK(launch_caf_begin(cw, K, f, s));
+  CafState* hst = reinterpret_cast<CafState*>(c->host);
+  std::vector<int32_t> nit, cv;
+  // every completed round zeroes a positive weight: at most K rounds; the state is read once
+  // per round, the round's power_iters applications are queued without looking
+  for (int64_t t = 0; t < K; ++t) {
+    HIPCHK(launch_caf_round(cw, K, f, power_iters, power_tol, s));
+    HIPCHK(hipMemcpyAsync(hst, cw.st, sizeof(CafState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (hst->rounds > (int32_t)nit.size()) {
+      nit.push_back(hst->iters);
+      cv.push_back(hst->converged);
+    }
+    if (hst->loop_done) break;
+  }
+  if (stop == 2) return GM_OK;
+  HIPCHK(launch_caf_weighted_mean(X, K, d, ldx, ws, cw.cbest, cw, out, s));
+  if (weights)
+    HIPCHK(hipMemcpyAsync(weights, cw.cbest, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, s));
+  if (eigenvalue) *eigenvalue = hst->rounds > 0 ? hst->best : nan;
+  if (weight) *weight = hst->Sbest;
+  if (rounds) *rounds = hst->rounds;
+  if (best_round) *best_round = hst->best_round;
+  for (size_t t = 0; t < nit.size(); ++t) {
+    if (niter) niter[t] = nit[t];
+    if (converged) converged[t] = cv[t];
+  }
+  return GM_OK;
+}
+
+int gm_weighted_mean_f32(gm_ctx* c, const float* X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout, const double* weights, float* out, void* stream) {
+  if (!c || !X || !weights || !out || K < 1 || d < 0 || !known_layout(layout))
+    return fail(GM_ERR_INVALID, "gm_weighted_mean_f32: bad args (a NULL ctx, X, weights or out, "
+                "K < 1, d < 0 or an unknown layout)");
+  if (K > 4096)
+    return fail(GM_ERR_UNSUPPORTED, "gm_weighted_mean_f32: K <= 4096 (got %lld)", (long long)K);
+  int ws = 0;
+  int rc = robust_shift("gm_weighted_mean_f32", K, d, ldx, layout, &ws);
+  if (rc) return rc;
+  if (d == 0) return GM_OK;
+  const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  WsOrder order(c, s);
+  HIPCHK(order.err);
+  CafWork cw{};
+  rc = grow_ws(c, caf_layout(nullptr, K, &cw));
+  if (rc) return rc;
+  caf_layout(c->ws, K, &cw);
+  HIPCHK(launch_caf_weighted_mean(X, K, d, ldx, ws, weights, cw, out, s));
   return GM_OK;
 }
 

@@ -504,6 +504,60 @@ hipError_t launch_dnc_scores(const DncWork& w, int64_t K, int64_t n, double* sco
 // good[i] = flag[i] (first) or good[i] & flag[i].
 hipError_t launch_dnc_and_flags(int32_t* good, const int32_t* flag, int64_t K, bool first,
                                 hipStream_t s);
+// The covariance filter's K-space solver and weighted mean (caf.hip; the definition is in
+// include/gmagg.h).  Everything but the last pass works on D [K][K] (launch_krum_dist) and
+// O(K) fp64 state; the host reads CafState once per round.
+struct CafState {
+  int32_t loop_done;    // no further round runs (every later launch is a no-op)
+  int32_t it_done;      // the round's power iteration has ended (its launches are no-ops)
+  int32_t iters;        // applications of M in this round
+  int32_t converged;    // the movement test passed (or ||M e_r|| == 0)
+  int32_t failed;       // a non-finite norm (a zero one inside the iteration): the loop ends
+  int32_t degenerate;   // ||M e_r|| == 0: lambda = 0, no iteration
+  int32_t rounds;       // rounds that reached step 3
+  int32_t best_round;   // t*
+  int32_t recorded;     // c* has been written
+  int32_t round;        // t of the round in flight
+  int32_t r;            // the start row
+  int32_t pad;
+  double S;             // sum c_k of the round in flight
+  double best;          // lambda of round t* (+inf before the first)
+  double Sbest;         // S*
+  double lambda;        // the last round's
+  double q, sz, rz;     // p.a / 2, 1.z and rho.z of the current iterate
+  double nrm, movement; // of the last application
+};
+struct CafHead {
+  double S;             // sum of the positive weights
+  int32_t m;            // rows listed
+  int32_t pad;
+};
+struct CafWork {
+  double* D;            // [K][K], both triangles after launch_caf_begin
+  CafState* st;
+  CafHead* head;
+  double *c, *cbest;    // [K] the weights in flight, and c*
+  double *p, *sp;       // [K] c / S and its square root
+  double *rho;          // [K] ||u_k||^2
+  double *w, *z;        // [K] the unit iterate, and sqrt(p) o w
+  double* y;            // [K] the last product with D
+  double* coef;         // [K] c*_k / S* of the listed rows
+  int32_t* list;        // [K] the rows with c*_k > 0, increasing
+};
+// Carves everything but D out of `base` (nullptr: sizes only); the bytes needed.
+size_t caf_layout(char* base, int64_t K, CafWork* w);
+// Mirrors D's upper triangle (w.D == nullptr: no D, only the weights are wanted) and sets c = 1,
+// S = K and the fresh state (loop_done when f == 0).
+hipError_t launch_caf_begin(const CafWork& w, int64_t K, int64_t f, hipStream_t s);
+// One round: 2 power_iters + 4 launches, all no-ops once the loop has ended.
+hipError_t launch_caf_round(const CafWork& w, int64_t K, int64_t f, int64_t power_iters,
+                            double tol, hipStream_t s);
+// out = float(sum over the rows with c_k > 0, increasing k, of (c_k / sum of those c) x_k), the
+// sum of c in caf_sum's order; rows with c_k <= 0 or NaN are not read.  Writes w.coef, w.list
+// and w.head.
+hipError_t launch_caf_weighted_mean(const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                                    const double* c, const CafWork& w, float* out,
+                                    hipStream_t s);
 // The omniscient attacks (attack.hip), in place: rows H .. K-1 of X are overwritten from the
 // statistics of rows 0 .. H-1; ws = log2 of the panel width (0: rows), ldx the row or panel
 // stride.  Any alignment (4-column vector items where the base and stride allow).

@@ -20,7 +20,7 @@ the 32-wave rows kernel; equal to rounding otherwise.
 ``fltrust``, ``clip`` / ``arc``, the attacks and, under ``options={"bf16": True}``, ``mean`` /
 ``median`` / ``trimmed_mean`` (coordinate_bf16.hip: the selections on 16-bit order keys; without
 the option those three stay fp32 and raise on bf16); ``Krum``, ``meamed``, ``multi_krum``,
-``bulyan``, ``nnm`` and ``dnc`` take fp32 panels only.  ``bucketing`` (s-bucketing,
+``bulyan``, ``nnm``, ``dnc`` and ``caf`` take fp32 panels only.  ``bucketing`` (s-bucketing,
 aggregators.py) reads fp32 and bf16 panels alike and writes its fp32 bucket means as
 ``ClientPanels(ceil(K/s), d)``, whose panel width is that of the smaller K.
 """

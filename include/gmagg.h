@@ -583,6 +583,95 @@ int gm_dnc_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, i
                int64_t power_iters, double power_tol, float* out, double* scores, int32_t* good,
                int64_t* n_good, int32_t* niter, int32_t* converged, void* stream);
 
+/* CAF, the covariance filter: the down-weighting spectral filter of robust mean estimation
+ * (Diakonikolas, Kamath, Kane, Li, Moitra & Stewart, "Being Robust (in High Dimensions) Can Be
+ * Practical", ICML 2017), which ByzFL ships as the Covariance-bound Agnostic Filter and attributes
+ * to Allouah, Guerraoui & Stephan (2025).  It looks at the top eigen-direction of the weighted
+ * covariance over all d coordinates (DnC looks at a sample of them) and needs only f, no bound on
+ * the honest covariance.  Where ByzFL's code differs from this text, this text holds.
+ *
+ * Inputs: rows x_k, k < K, fp32 widened exactly; f = the number of Byzantine rows tolerated,
+ * K >= 2 and 0 <= 2f < K; power_iters >= 1 (Python default 100) and power_tol >= 0 (1e-10).
+ *
+ * All arithmetic is fp64.  State: weights c_k = 1 and best = +inf.  Every sum over k runs in a
+ * fixed order that depends on K alone.
+ *
+ * Round t = 0, 1, ..., run while S = sum_k c_k > K - 2f:
+ * 1. p_k = c_k / S;  mu = sum_k p_k x_k;  u_k = x_k - mu;  M_ij = sqrt(p_i) sqrt(p_j) (u_i . u_j).
+ *    M is K x K and positive semidefinite, with the nonzero spectrum of the weighted covariance
+ *    sum_k p_k u_k u_k^T.
+ * 2. The top eigenpair of M by power iteration.
+ *    - Start: r = arg max_k M_kk (NaN first, ties to the lower index), w_0 = M e_r / ||M e_r||.
+ *    - Step: w_i = M w_{i-1} / ||.||, one "application".
+ *    - Stop when ||w_i - w_{i-1}||_2 <= power_tol, or after power_iters applications.
+ *    - lambda = w^T M w of the last unit iterate, converged or not.
+ *    - ||M e_r|| = 0 (all weighted rows equal): lambda = 0 with 0 applications, converged = 1;
+ *      step 3 runs, then the loop ends.
+ *    - A non-finite norm or lambda (and a zero norm inside the iteration, which cannot be
+ *      normalised) ends the loop at once; if nothing has been recorded yet, the current c is.
+ *      Such a round is not counted in `rounds`.
+ * 3. If lambda < best (strict): best = lambda, c* = c, S* = S, t* = t.
+ * 4. g_k = u_k . (sum_j sqrt(p_j) w_j u_j), tau_k = g_k^2, tau_max = the maximum over the rows
+ *    with c_k > 0.  tau_max zero or non-finite ends the loop.  Otherwise
+ *    c_k <- c_k (1 - tau_k / tau_max) for every row with c_k > 0: the arg-max row becomes exactly
+ *    0 and a zero weight stays zero.  (The normalisation of the direction cancels in the ratio.)
+ * Every completed round zeroes at least one positive weight, so the loop ends within K rounds;
+ * the host caps it there.
+ *
+ * Result: out_j = float( sum_{k : c*_k > 0, increasing k} (c*_k / S*) x_kj ), fp64 sums rounded
+ * once.  A row of weight 0 is skipped, not multiplied: whatever it holds contributes nothing and
+ * the result pass does not read it.  f = 0 runs no round: the result is gm_mean_f32's, bit for
+ * bit, with c* = 1, S* = K, rounds = 0 and a NaN eigenvalue.
+ *
+ * What is actually built (the K-space identities).  With D_ij = ||x_i - x_j||^2 (the exact
+ * distance path of Krum, Multi-Krum and NNM: fp32 differences, fp32 squares summed per 32-column
+ * stage, fp64 across stages), a = D p, q = p^T a / 2 and rho_k = ||u_k||^2 = a_k - q:
+ *     u_i . u_j = (rho_i + rho_j - D_ij) / 2
+ *     G z = (rho (1^T z) + 1 (rho^T z) - D z) / 2          for any z,  G = (u_i . u_j)
+ *     M w = sqrt(p) o G (sqrt(p) o w),      g = G (sqrt(p) o w)
+ * so one application of M is one product with the fixed matrix D plus two dot products, the
+ * d x d covariance is never formed and X is read twice: once for D, once for the result.
+ *
+ * What the filter does not defend against: a non-finite entry makes D non-finite and ends the
+ * filter in round 0 with c = 1; the result is then the plain weighted mean under IEEE rules
+ * (NaN in the columns that hold it).  Compose with gm_clip_rows_f32 (clip / arc) for that.
+ *
+ * The result and every reported quantity are bit-identical for rows, panels and every alignment.
+ *
+ *   X          fp32, layout GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any alignment: 16-byte loads where
+ *              the base and ldx allow) or GM_LAYOUT_PANELS ([ceil(d/W)][K][W], W =
+ *              gm_panel_width(K), ldx = panel stride >= K*W).  Never written.
+ *   out        device fp32 [d].
+ *   weights    device double [K], or NULL: c*.
+ *   eigenvalue, weight   host, or NULL: lambda of round t* (NaN when no round was counted), S*.
+ *   rounds, best_round   host, or NULL: the rounds that reached step 3, and t*.
+ *   niter, converged     host int32 [K], or NULL: per counted round the applications run and
+ *              whether the movement test passed; the first *rounds entries are written.
+ * Uses the context's workspace (stream-ordered with the other calls on it): D (8 K^2 bytes), the
+ * distance pass's partials and O(K) state.  The call blocks once per round (the host reads one
+ * small state record to decide whether another round is queued), never per application; the
+ * weighted mean is queued behind the last round and takes the rows and weights from device memory.
+ * GM_ERR_INVALID (nothing written): a NULL ctx, X or out, K < 2, d < 0, f < 0, 2f >= K, an unknown
+ * layout, a rows layout with ldx < d (a panel stride < K*W), power_iters < 1, power_tol not >= 0.
+ * GM_ERR_UNSUPPORTED (with a message): K > 4096, a panel layout whose K has no panel width, a
+ * d-sharded or collective context (the distances would need a K x K all-reduce).
+ * d == 0 returns GM_OK, launches nothing and writes nothing. */
+int gm_caf_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, int32_t layout,
+               int64_t f, int64_t power_iters, double power_tol, float* out, double* weights,
+               double* eigenvalue, double* weight, int32_t* rounds, int32_t* best_round,
+               int32_t* niter, int32_t* converged, void* stream);
+
+/* CAF's result pass on its own: out_j = float( sum_{k : w_k > 0, increasing k} (w_k / S) x_kj ),
+ * S = the sum of the positive weights, fp64 sums rounded once.  A row whose weight is zero,
+ * negative or NaN is skipped and not read.  With gm_caf_f32's `weights` on the same X this is that
+ * call's out, bit for bit; no positive weight gives zeros.
+ *   X, out     as gm_caf_f32's.   weights   device double [K].
+ * No host synchronisation; works on a d-sharded context (columns are independent).
+ * GM_ERR_INVALID (nothing written): a NULL pointer, K < 1, d < 0, an unknown layout, ldx too small.
+ * GM_ERR_UNSUPPORTED: K > 4096, a panel layout whose K has no panel width.  d == 0: GM_OK. */
+int gm_weighted_mean_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx,
+                         int32_t layout, const double* weights, float* out, void* stream);
+
 /* FLTrust (Cao, Fang, Liu & Gong, "FLTrust: Byzantine-robust Federated Learning via Trust
  * Bootstrapping", NDSS 2021): the only rule here that scores a client against a reference vector,
  * the server's own update, instead of against the other clients.
