@@ -10,7 +10,7 @@ reference's training loop.
 """
 from .aggregators import (GMResult, Krum, OMA, arc, bucketed, bucketing, bulyan, caf,  # noqa: F401
                           cclip, clip, clipped, context, dnc, fltrust, gm, gm2, meamed, mean, median,
-                          mixed, multi_krum, nnm, trimmed_mean)
+                          mixed, multi_krum, nnm, pair_distances, trimmed_mean)
 from .attacks import alie, ipm, minmax, minsum, z_max  # noqa: F401
 from .panels import ClientPanels, panel_width  # noqa: F401
 

@@ -23,6 +23,7 @@ GM_GUARD_NONE, GM_GUARD_ACCEPTED, GM_GUARD_REJECTED, GM_GUARD_ACCEPTED_FLOOR = 0
 GM_EXCHANGE_NONE, GM_EXCHANGE_AGENT, GM_EXCHANGE_XCD_LOCAL, GM_EXCHANGE_XCD_HIER = 0, 1, 2, 3
 GM_EXCHANGE_XCD_SPLIT = 4
 GM_CLIP_STATIC, GM_CLIP_ARC = 0, 1
+GM_DIST_EXACT, GM_DIST_MFMA = 0, 1
 
 NOISE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_float),
                        C.POINTER(C.c_float), C.POINTER(C.c_float))
@@ -122,6 +123,15 @@ SIGNATURES = [
     ("gm_bulyan_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _P, _P, _P]),
     ("gm_nnm_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _P, _I64, C.c_int32, _P,
                              _P]),
+    ("gm_krum_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, C.c_int32, _P,
+                               C.POINTER(_I64), _P]),
+    ("gm_multi_krum_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, _I64, C.c_int32,
+                                     _P, _P, _P]),
+    ("gm_nnm_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _I64, C.c_int32, _P, _I64,
+                              C.c_int32, _P, _P]),
+    ("gm_pair_dist_bf16", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, _P, _P]),
+    ("gm_pair_dist_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _P]),
+    ("gm_dist_last_info", C.c_int, [_P, C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("gm_dnc_f32", C.c_int, [_P, _P, _I64, _I64, _I64, C.c_int32, _P, _I64, _I64, _I64, _I64,
                              C.c_double, _P, _P, C.POINTER(C.c_int32), C.POINTER(_I64),
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),

@@ -710,9 +710,66 @@ trimmed_mean.__doc__ = f"""Coordinate-wise mean without the int(0.1 K) smallest 
     {_BF16_INPUT}"""
 
 
+_DIST_MODES = {"exact": _lib.GM_DIST_EXACT, "mfma": _lib.GM_DIST_MFMA}
+_DIST_REASONS = ("ok", "requested_exact", "not_eligible", "nonfinite_fallback")
+
+
+def _dist_request(wList, bf16, distances, who: str):
+    """(reads bf16, dist_mode) of a distance-family call, from checks that touch no device.
+    `distances` must be "exact" or "mfma" (ValueError); the MFMA tier reads bf16, so "mfma" on
+    fp32 input is a ValueError.  bf16 input without the opt-in is not decided here: the caller's
+    fp32 path refuses it (TypeError) as before."""
+    if distances not in _DIST_MODES:
+        raise ValueError(f"{who}: distances must be 'exact' or 'mfma' (got {distances!r})")
+    dtype = wList.data.dtype if isinstance(wList, ClientPanels) else getattr(wList, "dtype", None)
+    is_bf16 = bool(bf16) and dtype == torch.bfloat16
+    if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{who} reads fp32 or, when asked to, bf16 client updates (got {dtype})")
+    if dtype == torch.bfloat16 and not bf16:
+        raise TypeError(f"{who} is fp32 only (got torch.bfloat16) unless bf16 is asked for: "
+                        "options={'bf16': True}, nnm / pair_distances: bf16=True")
+    if distances == "mfma" and dtype == torch.float32:
+        raise ValueError(f"{who}: distances='mfma' reads bf16 client updates (got torch.float32); "
+                         "fp32 input has the exact distances only")
+    return is_bf16, _DIST_MODES[distances]
+
+
+def _dist_info(ctx) -> dict:
+    """gm_dist_last_info of ctx (waits for the stream of its last bf16 distance call)."""
+    info = (C.c_int64 * 4)()
+    beta = C.c_double()
+    _lib.check(ctx.lib.gm_dist_last_info(ctx.handle, info, C.byref(beta)), "gm_dist_last_info")
+    return {"tier": ("exact", "mfma")[info[0]], "reason": _DIST_REASONS[info[1]],
+            "slices": info[2], "flush": info[3], "beta": beta.value}
+
+
+_FP32_DIST_INFO = {"tier": "exact", "reason": "requested_exact", "slices": None, "flush": 32,
+                   "beta": None}
+
+
 def Krum(wList, options):  # noqa: N802 - reference name (M:197)
     """The row with the smallest sum of squared distances to its honestSize-1
-    nearest rows, itself included (M:197-204)."""
+    nearest rows, itself included (M:197-204).  With ``options["bf16"]`` true a bf16 [K, d]
+    tensor (unit-stride rows are read in place at any alignment) or bf16 ClientPanels is read as
+    it is: ``options["distances"]`` "exact" (the default) returns the bits of the fp32 call on
+    ``wList.float()``; "mfma" takes the distances from the bf16 matrix cores within
+    ``Krum.last_info["beta"] * (rho_i + rho_j)`` (``multi_krum``).  Without the option bf16 is
+    refused (TypeError) before a GPU is touched.  ``Krum.last_info["algo"]`` is "exact", "gram"
+    or "mfma"."""
+    bf16, mode = _dist_request(wList, options.get("bf16"), options.get("distances", "exact"),
+                               "Krum")
+    if bf16:
+        X, ldx, layout, K, d = _operand(wList, bf16=True)
+        out = torch.empty(d, dtype=torch.float32, device=X.device)
+        idx = C.c_int64()
+        ctx = context(X.device)
+        ctx.call("gm_krum_bf16", X.data_ptr(), K, d, ldx, layout, int(options["honestSize"]),
+                 mode, out.data_ptr(), C.byref(idx), _stream_ptr(X.device))
+        info = _dist_info(ctx)
+        Krum.last_index = idx.value
+        Krum.last_info = {"algo": info["tier"], "candidates": 0, "reason": info["reason"],
+                          "beta": info["beta"], "slices": info["slices"]}
+        return _to_caller(out, wList)
     X, ldx, layout, K, d = _operand(wList)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     idx = C.c_int64()
@@ -759,8 +816,22 @@ def multi_krum(wList, options):
     The scores are Krum's on the exact distance path (GMAGG_KRUM is ignored); ``m == 1`` is
     that Krum row bit for bit.  wList: an fp32 [K, d] tensor or fp32 ClientPanels, K <= 4096,
     2 <= honestSize <= K + 1, 1 <= m <= K.  ``multi_krum.last_selected`` holds the selected
-    rows, increasing."""
-    K, d = _shape(wList, "multi_krum", max_k=4096)
+    rows, increasing.
+
+    ``options["bf16"]`` true also reads a bf16 [K, d] tensor (unit-stride rows in place, at any
+    alignment) or bf16 ClientPanels; without it bf16 raises TypeError before a GPU is touched.
+    ``options["distances"]``: "exact" (the default) is the fp32 kernels on the widened elements,
+    the bits of the fp32 call on ``wList.float()``; "mfma" (bf16 only, ValueError on fp32) forms
+    D~ = max(0, G_ii + G_jj - 2 G_ij) from G = X X^T on the bf16 matrix cores, with
+    |D~_ij - D_ij| <= beta (||x_i||^2 + ||x_j||^2): the selection can differ from the exact
+    tier's only between rows whose scores lie within that bound; the output is the same fp64
+    mean of whichever rows are selected.  Rows that are not 16-byte aligned or whose stride is
+    not a multiple of 8 take the exact tier (reason "not_eligible"), and so does input with a
+    NaN, an infinity or a square beyond fp32 (reason "nonfinite_fallback", decided on the
+    device).  ``multi_krum.last_info`` = {"tier", "reason", "slices", "flush", "beta"}."""
+    bf16, mode = _dist_request(wList, options and options.get("bf16"),
+                               (options or {}).get("distances", "exact"), "multi_krum")
+    K, d = _shape(wList, "multi_krum", bf16=bf16, max_k=4096)
     honest = _honest_size(options, "multi_krum")
     if not 2 <= honest <= K + 1:
         raise ValueError(f"multi_krum: honestSize {honest} not in [2, {K + 1}]")
@@ -768,17 +839,23 @@ def multi_krum(wList, options):
     m = honest if m is None else int(m)
     if not 1 <= m <= K:
         raise ValueError(f"multi_krum: m = {m} not in [1, {K}]")
-    X, ldx, layout, K, d = _operand(wList)
+    X, ldx, layout, K, d = _operand(wList, bf16=bf16)
     out = torch.empty(d, dtype=torch.float32, device=X.device)
     sel = (C.c_int32 * m)()
-    if d > 0:
+    multi_krum.last_info = dict(_FP32_DIST_INFO)
+    if d > 0 and bf16:
+        ctx = context(X.device)
+        ctx.call("gm_multi_krum_bf16", X.data_ptr(), K, d, ldx, layout, honest, m, mode,
+                 out.data_ptr(), sel, _stream_ptr(X.device))
+        multi_krum.last_info = _dist_info(ctx)
+    elif d > 0:
         context(X.device).call("gm_multi_krum_f32", X.data_ptr(), K, d, ldx, layout, honest, m,
                                out.data_ptr(), sel, _stream_ptr(X.device))
     multi_krum.last_selected = list(sel) if d > 0 else []
     return _to_caller(out, wList)
 
 
-multi_krum.last_selected = None
+multi_krum.last_selected = multi_krum.last_info = None
 
 
 def bulyan(wList, options):
@@ -914,7 +991,7 @@ def bucketed(aggregate, s, generator=None, layout="panels"):
                      f"{aggregate.__name__} on the bucket means of s = {s} bucketing", step)
 
 
-def nnm(wList, f, layout=None, neighbors=False):
+def nnm(wList, f, layout=None, neighbors=False, bf16=False, distances="exact"):
     """Nearest-neighbor mixing (Allouah, Farhadkhani, Guerraoui, Gupta, Pinot & Stephan, "Fixing
     by Mixing: A Recipe for Optimal Byzantine ML under Heterogeneity", AISTATS 2023, Algorithm
     1), the pre-step under which the robust rules reach the optimal heterogeneity bound: every
@@ -932,21 +1009,68 @@ def nnm(wList, f, layout=None, neighbors=False):
     rows as fp32: with ``layout=None`` a [K, d] tensor for a tensor and ``ClientPanels(K, d)``
     for ClientPanels; ``"rows"`` / ``"panels"`` force one.  ``neighbors=True`` returns
     ``(Y, N)`` with N the int32 [K, K - f] neighbour lists (increasing within a row) on the GPU.
-    bf16 inputs, d-sharded contexts and K > 4096 are refused."""
-    K, d = _shape(wList, "nnm", max_k=4096)
+    d-sharded contexts and K > 4096 are refused.
+
+    ``bf16=True`` also reads a bf16 [K, d] tensor (unit-stride rows in place, at any alignment)
+    or bf16 ClientPanels; the mixed rows stay fp32.  Without it bf16 input raises TypeError
+    before a GPU is touched.  ``distances``: "exact" (the default) gives the bits of the fp32
+    call on ``wList.float()``; "mfma" (bf16 only; ValueError on fp32) takes the distances from
+    the bf16 matrix cores within beta (||x_i||^2 + ||x_j||^2), so a neighbour list can differ
+    from the exact tier's only in members whose distances lie within that band of the list's
+    threshold, and every row of Y is still the fp64 mean of the rows its list names (tiers,
+    fallbacks and the reasons: ``multi_krum``).  ``nnm.last_info`` = {"tier", "reason",
+    "slices", "flush", "beta"}; a bf16 call waits for its stream to fill it in."""
+    bf16, mode = _dist_request(wList, bf16, distances, "nnm")
+    K, d = _shape(wList, "nnm", bf16=bf16, max_k=4096)
     f = _index(f, "nnm", "f", 0, K - 1)
     panels_out = _panels_out(layout, wList, K, "nnm")
-    X, ldx, lin, K, d = _operand(wList)
+    X, ldx, lin, K, d = _operand(wList, bf16=bf16)
     m = K - f
     out, Y, ldy, lout = _new_rows(K, d, X.device, panels_out)
     N = torch.empty(K, m, dtype=torch.int32, device=X.device) if neighbors else None
-    if d > 0:
+    nnm.last_info = dict(_FP32_DIST_INFO)
+    if d > 0 and bf16:
+        ctx = context(X.device)
+        ctx.call("gm_nnm_bf16", X.data_ptr(), K, d, ldx, lin, f, mode, Y.data_ptr(), ldy, lout,
+                 N.data_ptr() if neighbors else None, _stream_ptr(X.device))
+        nnm.last_info = _dist_info(ctx)
+    elif d > 0:
         context(X.device).call("gm_nnm_f32", X.data_ptr(), K, d, ldx, lin, f, Y.data_ptr(), ldy,
                                lout, N.data_ptr() if neighbors else None, _stream_ptr(X.device))
     elif neighbors:                      # every distance is 0: the m rows of lowest index
         N.copy_(torch.arange(m, dtype=torch.int32, device=X.device).expand(K, m))
     out = _to_caller(out, wList)
     return (out, N) if neighbors else out
+
+
+nnm.last_info = None
+
+
+def pair_distances(wList, bf16=False, distances="exact"):
+    """The K x K squared distances of the client updates, fp64 [K, K] on the GPU, full and
+    symmetric: the matrix Krum, multi_krum, nnm, bulyan and caf work on.  fp32 input (a [K, d]
+    tensor or ClientPanels): the exact path.  ``bf16=True`` also reads bf16 rows or bf16
+    ClientPanels, ``distances`` "exact" (the fp32 kernels on the widened elements: the bits of
+    ``pair_distances(wList.float())``) or "mfma" (the bf16 matrix cores, within
+    ``pair_distances.last_info["beta"]`` (||x_i||^2 + ||x_j||^2) of the exact-arithmetic
+    distances; bf16 only, ValueError on fp32; see ``multi_krum``).  K <= 4096."""
+    is_bf16, mode = _dist_request(wList, bf16, distances, "pair_distances")
+    K, d = _shape(wList, "pair_distances", bf16=is_bf16, max_k=4096)
+    X, ldx, layout, K, d = _operand(wList, bf16=is_bf16)
+    D = torch.zeros(K, K, dtype=torch.float64, device=X.device)
+    pair_distances.last_info = dict(_FP32_DIST_INFO)
+    if d > 0 and is_bf16:
+        ctx = context(X.device)
+        ctx.call("gm_pair_dist_bf16", X.data_ptr(), K, d, ldx, layout, mode, D.data_ptr(),
+                 _stream_ptr(X.device))
+        pair_distances.last_info = _dist_info(ctx)
+    elif d > 0:
+        context(X.device).call("gm_pair_dist_f32", X.data_ptr(), K, d, ldx, layout, D.data_ptr(),
+                               _stream_ptr(X.device))
+    return D
+
+
+pair_distances.last_info = None
 
 
 def mixed(aggregate, f=None, layout="panels"):
@@ -958,14 +1082,18 @@ def mixed(aggregate, f=None, layout="panels"):
 
     f: the number of Byzantine clients to mix against; None takes ``K - options['honestSize']``
     per call (ValueError without it).  Options pass through unchanged (NNM keeps all K rows, so
-    ``honestSize`` stands); the caller's dict is not modified.  The result lives on
-    wList.device, as the aggregators' own."""
+    ``honestSize`` stands); the caller's dict is not modified.  The mixing step itself reads
+    ``options["bf16"]`` and ``options["distances"]`` (``nnm``'s arguments of those names), so
+    ``mixed(gm2)(Xbf16, {"bf16": True, "distances": "mfma"})`` mixes bf16 rows on the fast
+    distances.  The result lives on wList.device, as the aggregators' own."""
     _panels_out(layout, None, None, "mixed")
 
     def step(wList, options, name):
         K = int(wList.shape[0])
         f_ = f if f is not None else K - _honest_size(options, name)
-        return nnm(wList, f_, layout=_handover(layout, K)), options
+        # (only what the call's options name: without them nnm is called as before)
+        tier = {k: options[k] for k in ("bf16", "distances") if options and k in options}
+        return nnm(wList, f_, layout=_handover(layout, K), **tier), options
 
     return _pre_step(aggregate, "nnm",
                      f"{aggregate.__name__} on the rows mixed by nearest-neighbor mixing", step)

@@ -50,6 +50,7 @@ int gm_ctx_destroy(gm_ctx* c) {
   if (c->stage) (void)hipFree(c->stage);
   if (c->shadow) (void)hipFree(c->shadow);
   if (c->host) (void)hipHostFree(c->host);
+  if (c->dist_flag) (void)hipHostFree(c->dist_flag);
   for (auto e : c->poll_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto e : c->ev_free) (void)hipEventDestroy(e);

@@ -7,6 +7,7 @@
 // median / trimmed_mean select order statistics bit by bit (col_select below);
 // sums are fp64, rounded once.
 #include <algorithm>
+#include <type_traits>
 
 #include "device_util.h"
 #include "gmagg_internal.h"
@@ -757,11 +758,16 @@ constexpr int kPT = 128;   // pair-tile edge (rows)
 constexpr int kPC = 32;    // columns per LDS stage
 constexpr int kPDT = 512;  // pair_dist threads per block
 
-template <bool VEC>
-__global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, int64_t K,
-                                                 int64_t d, int64_t ldx, int ws, int64_t chunk,
-                                                 double* __restrict__ part) {
+// The element type T is float or uint16_t (bf16 bit patterns, widened at the load: exact, so
+// everything after the load is the fp32 kernel's).  bf16 stages are loaded one 16-byte group of
+// 8 columns per thread and row tile (VEC: base 16-byte aligned, ldx % 8 == 0), else by element.
+template <typename T, bool VEC>
+__device__ __forceinline__ void pair_dist_body(const T* __restrict__ X, int64_t K, int64_t d,
+                                               int64_t ldx, int ws, int64_t chunk,
+                                               double* __restrict__ part) {
   typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  constexpr bool B16 = std::is_same<T, uint16_t>::value;
   __shared__ __attribute__((aligned(16))) float sA[kPC][kPT + 4];
   __shared__ __attribute__((aligned(16))) float sB[kPC][kPT + 4];
   const int64_t nT = (K + kPT - 1) / kPT;
@@ -778,7 +784,30 @@ __global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, i
   // stage loads: thread owns (row r, columns cg..cg+3) of both row tiles for q = 0..1;
   // the next stage's loads are issued before this stage's arithmetic (register prefetch)
   f4 pre[2][2];
+  u4 pre16[2];     // bf16: thread owns (row r16, columns cg16..cg16+7) of both row tiles
+  const int r16 = threadIdx.x >> 2, cg16 = (threadIdx.x & 3) * 8;
   auto load_stage = [&](int64_t c0) {
+    if constexpr (B16) {
+      const int64_t col = c0 + cg16;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int64_t row = (t ? bj : bi) * kPT + r16;
+        u4 v = {0u, 0u, 0u, 0u};
+        if (row < K && col < ce) {
+          const uint16_t* src = elem(X, ldx, ws, row, col);
+          if (VEC && col + 8 <= ce) {
+            v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(src));
+          } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+              const uint32_t h = col + u < ce ? (uint32_t)src[u] : 0u;
+              v[u >> 1] |= h << (16 * (u & 1));
+            }
+          }
+        }
+        pre16[t] = v;
+      }
+    } else {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int idx = threadIdx.x + kPDT * q, r = idx >> 3, cg = (idx & 7) * 4;
@@ -799,10 +828,19 @@ __global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, i
         pre[q][t] = v;
       }
     }
+    }
   };
   if (cb < ce) load_stage(cb);
   for (int64_t c0 = cb; c0 < ce; c0 += kPC) {
     __syncthreads();
+    if constexpr (B16) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int sh = 16 * (u & 1);
+        sA[cg16 + u][r16] = __uint_as_float(((pre16[0][u >> 1] >> sh) & 0xFFFFu) << 16);
+        sB[cg16 + u][r16] = __uint_as_float(((pre16[1][u >> 1] >> sh) & 0xFFFFu) << 16);
+      }
+    } else {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int idx = threadIdx.x + kPDT * q, r = idx >> 3, cg = (idx & 7) * 4;
@@ -811,6 +849,7 @@ __global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, i
         sA[cg + u][r] = pre[q][0][u];
         sB[cg + u][r] = pre[q][1][u];
       }
+    }
     }
     __syncthreads();
     if (c0 + kPC < ce) load_stage(c0 + kPC);
@@ -852,11 +891,28 @@ __global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, i
   }
 }
 
+template <bool VEC>
+__global__ void __launch_bounds__(kPDT) pair_dist(const float* __restrict__ X, int64_t K,
+                                                 int64_t d, int64_t ldx, int ws, int64_t chunk,
+                                                 double* __restrict__ part) {
+  pair_dist_body<float, VEC>(X, K, d, ldx, ws, chunk, part);
+}
+// bf16 rows or panels.  gate (nullable, device): the launch is a no-op while *gate == 0 (the
+// fallback of pairdist_bf16.hip: enqueued always, run only when the flag is up).
+template <bool VEC>
+__global__ void __launch_bounds__(kPDT) pair_dist_bf16(const uint16_t* __restrict__ X, int64_t K,
+                                                      int64_t d, int64_t ldx, int ws,
+                                                      int64_t chunk, double* __restrict__ part,
+                                                      const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;                      // (block-uniform)
+  pair_dist_body<uint16_t, VEC>(X, K, d, ldx, ws, chunk, part);
+}
+
 // D[i][j] (i <= j: the tile of (i, j) has bi <= bj, so it was computed) = the sum
 // over slices in slice order; one wave per 64 consecutive elements, 4 waves split
 // the slices and combine in a fixed order (deterministic, no atomics).
-__global__ void __launch_bounds__(256) pair_reduce(const double* __restrict__ part, int64_t S,
-                                                   int64_t K, double* __restrict__ D) {
+__device__ __forceinline__ void pair_reduce_body(const double* __restrict__ part, int64_t S,
+                                                 int64_t K, double* __restrict__ D) {
   __shared__ double red[4][64];
   const int64_t n = K * K;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -872,6 +928,17 @@ __global__ void __launch_bounds__(256) pair_reduce(const double* __restrict__ pa
   red[w][lane] = s;
   __syncthreads();
   if (w == 0 && on) D[e] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+__global__ void __launch_bounds__(256) pair_reduce(const double* __restrict__ part, int64_t S,
+                                                   int64_t K, double* __restrict__ D) {
+  pair_reduce_body(part, S, K, D);
+}
+__global__ void __launch_bounds__(256) pair_reduce_gated(const double* __restrict__ part,
+                                                         int64_t S, int64_t K,
+                                                         double* __restrict__ D,
+                                                         const int* __restrict__ gate) {
+  if (*gate == 0) return;                              // (block-uniform)
+  pair_reduce_body(part, S, K, D);
 }
 
 // Krum, step 2 (one block per row): score_i = sum of the kk smallest D[i][*] (self
@@ -904,14 +971,15 @@ __global__ void __launch_bounds__(64) krum_argmin(const double* __restrict__ sco
 }
 
 // Krum, step 4: out = row *index, grid-wide copy.
-__global__ void __launch_bounds__(256) copy_row(const float* __restrict__ X, int64_t d,
+template <typename T>
+__global__ void __launch_bounds__(256) copy_row(const T* __restrict__ X, int64_t d,
                                                 int64_t ldx, int ws,
                                                 const int64_t* __restrict__ index,
                                                 float* __restrict__ out) {
   const int64_t k = *index;
   for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < d;
        c += (int64_t)gridDim.x * blockDim.x)
-    out[c] = *elem(X, ldx, ws, k, c);
+    out[c] = widen(*elem(X, ldx, ws, k, c));
 }
 
 // ---------------------------------------------------------------------------
@@ -1176,12 +1244,13 @@ __global__ void __launch_bounds__(64) krum_cand_argmin(const double* __restrict_
 }
 
 // out = row k (k on the host)
-__global__ void __launch_bounds__(256) copy_row_k(const float* __restrict__ X, int64_t d,
+template <typename T>
+__global__ void __launch_bounds__(256) copy_row_k(const T* __restrict__ X, int64_t d,
                                                   int64_t ldx, int ws, int64_t k,
                                                   float* __restrict__ out) {
   for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < d;
        c += (int64_t)gridDim.x * blockDim.x)
-    out[c] = *elem(X, ldx, ws, k, c);
+    out[c] = widen(*elem(X, ldx, ws, k, c));
 }
 
 static int grid_cols(int64_t d) {
@@ -1347,12 +1416,21 @@ int64_t krum_slices(int64_t K, int64_t d) {
   return best;
 }
 
-hipError_t launch_copy_row_k(const float* X, int64_t d, int64_t ldx, int ws, int64_t k, float* out,
-                             hipStream_t s) {
+template <typename T>
+static hipError_t copy_row_k_t(const T* X, int64_t d, int64_t ldx, int ws, int64_t k, float* out,
+                               hipStream_t s) {
   if (d > 0)
-    hipLaunchKernelGGL(copy_row_k, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
+    hipLaunchKernelGGL(copy_row_k<T>, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
                        dim3(256), 0, s, X, d, ldx, ws, k, out);
   return hipGetLastError();
+}
+hipError_t launch_copy_row_k(const float* X, int64_t d, int64_t ldx, int ws, int64_t k, float* out,
+                             hipStream_t s) {
+  return copy_row_k_t(X, d, ldx, ws, k, out, s);
+}
+hipError_t launch_copy_row_k(const uint16_t* X, int64_t d, int64_t ldx, int ws, int64_t k,
+                             float* out, hipStream_t s) {
+  return copy_row_k_t(X, d, ldx, ws, k, out, s);
 }
 
 hipError_t launch_krum_gram_select(const double* G, int KP, int64_t K, int64_t kk, double epsg,
@@ -1403,7 +1481,7 @@ hipError_t launch_krum_pick(const double* score, const int64_t* cidx, int64_t m,
                             hipStream_t s) {
   hipLaunchKernelGGL(krum_cand_argmin, dim3(1), dim3(64), 0, s, score, cidx, m, index);
   if (d > 0)
-    hipLaunchKernelGGL(copy_row, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
+    hipLaunchKernelGGL(copy_row<float>, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
                        dim3(256), 0, s, X, d, ldx, ws, index, out);
   return hipGetLastError();
 }
@@ -1434,6 +1512,44 @@ hipError_t launch_krum_scores(const double* D, int64_t K, int64_t kk, double* sc
   return hipGetLastError();
 }
 
+// bf16 rows or panels (pair_dist_bf16); gate: see pair_dist_bf16 (nullptr: always run).
+hipError_t launch_krum_dist(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                            double* D, double* part, const int* gate, hipStream_t s) {
+  const int64_t nT = (K + kPT - 1) / kPT, pairs = nT * (nT + 1) / 2;
+  const int64_t S = krum_slices(K, d);
+  const int64_t chunk = ((d + S - 1) / S + kPC - 1) / kPC * kPC;
+  const bool vec = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 8 == 0;
+  if (vec)
+    hipLaunchKernelGGL(pair_dist_bf16<true>, dim3((unsigned)pairs, (unsigned)S), dim3(kPDT), 0, s,
+                       X, K, d, ldx, ws, chunk, part, gate);
+  else
+    hipLaunchKernelGGL(pair_dist_bf16<false>, dim3((unsigned)pairs, (unsigned)S), dim3(kPDT), 0,
+                       s, X, K, d, ldx, ws, chunk, part, gate);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 g((unsigned)((K * K + 63) / 64));
+  if (gate)
+    hipLaunchKernelGGL(pair_reduce_gated, g, dim3(256), 0, s, part, S, K, D, gate);
+  else
+    hipLaunchKernelGGL(pair_reduce, g, dim3(256), 0, s, part, S, K, D);
+  return hipGetLastError();
+}
+
+// krum_argmin on the scores, then out = that row (widened where X is bf16).
+template <typename T>
+static hipError_t krum_pick_row(const double* score, int64_t K, const T* X, int64_t d, int64_t ldx,
+                                int ws, int64_t* index, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(krum_argmin, dim3(1), dim3(64), 0, s, score, K, index);
+  if (d > 0)
+    hipLaunchKernelGGL(copy_row<T>, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
+                       dim3(256), 0, s, X, d, ldx, ws, index, out);
+  return hipGetLastError();
+}
+hipError_t launch_krum_argmin_row(const double* score, int64_t K, const uint16_t* X, int64_t d,
+                                  int64_t ldx, int ws, int64_t* index, float* out, hipStream_t s) {
+  return krum_pick_row(score, K, X, d, ldx, ws, index, out, s);
+}
+
 hipError_t launch_krum(const float* X, int64_t K, int64_t d, int64_t ldx, int64_t kk, double* D,
                        double* part, double* score, float* out, int64_t* index, hipStream_t s,
                        int ws) {
@@ -1441,11 +1557,7 @@ hipError_t launch_krum(const float* X, int64_t K, int64_t d, int64_t ldx, int64_
   if (e != hipSuccess) return e;
   e = launch_krum_scores(D, K, kk, score, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(krum_argmin, dim3(1), dim3(64), 0, s, score, K, index);
-  if (d > 0)
-    hipLaunchKernelGGL(copy_row, dim3((unsigned)std::min<int64_t>((d + 255) / 256, 2048)),
-                       dim3(256), 0, s, X, d, ldx, ws, index, out);
-  return hipGetLastError();
+  return krum_pick_row(score, K, X, d, ldx, ws, index, out, s);
 }
 
 }  // namespace gmk

@@ -345,6 +345,38 @@ hipError_t launch_krum_dist(const float* X, int64_t K, int64_t d, int64_t ldx, i
                             double* part, hipStream_t s);
 hipError_t launch_krum_scores(const double* D, int64_t K, int64_t kk, double* score,
                               hipStream_t s);
+// The exact tier on bf16 bit patterns (rows at any 2-byte alignment, or bf16 panels): the same
+// kernels with the element widened at the load, so every result is the fp32 function's on the
+// widened matrix, bit for bit.  gate (nullable, device): while *gate == 0 both distance
+// launches are no-ops (the MFMA tier's fallback, pairdist_bf16.hip).
+hipError_t launch_krum_dist(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                            double* D, double* part, const int* gate, hipStream_t s);
+// index = the first argmin of score [K]; out = that row of X, widened.
+hipError_t launch_krum_argmin_row(const double* score, int64_t K, const uint16_t* X, int64_t d,
+                                  int64_t ldx, int ws, int64_t* index, float* out, hipStream_t s);
+hipError_t launch_copy_row_k(const uint16_t* X, int64_t d, int64_t ldx, int ws, int64_t k,
+                             float* out, hipStream_t s);
+hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, const uint16_t* X,
+                                  int64_t d, int64_t ldx, int ws, int32_t* flag, int32_t* list,
+                                  float* out, hipStream_t s);
+hipError_t launch_gather_mean(const uint16_t* X, int64_t d, int64_t ldx, int ws,
+                              const int32_t* list, int64_t m, float* out, hipStream_t s);
+hipError_t launch_nnm_mix(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                          const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
+                          hipStream_t s);
+// The MFMA tier (pairdist_bf16.hip): D~ = max(0, G_ii + G_jj - 2 G_ij) from G = X X^T on the
+// bf16 matrix cores, into D [K][K] (upper triangle), with the bound |D~ - D| <=
+// pairdist_mfma_beta() (rho_i + rho_j).  X: bf16 rows (16-byte aligned, ldx % 8 == 0) or bf16
+// panels.  part [pairdist_mfma_slices(K, d, num_cu)][K][K] fp64, rho [K] fp64 scratch; *flag
+// (device, zeroed by the launcher) is raised when a G_ii is not finite.
+constexpr int kMfmaFlush = 256;    // C: columns between two flushes of the fp32 accumulators
+double pairdist_mfma_beta();
+int64_t pairdist_mfma_slices(int64_t K, int64_t d, int num_cu);
+hipError_t launch_pairdist_mfma(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                                int num_cu, double* part, double* rho, double* D, int* flag,
+                                hipStream_t s);
+// D's lower triangle from its upper one (gm_pair_dist_bf16's full symmetric output).
+hipError_t launch_mirror_upper(double* D, int64_t K, hipStream_t s);
 // MeaMed, Multi-Krum and Bulyan (robust.hip).
 // The mean of the `keep` values of each column nearest to its lower median, over rows
 // rows[0 .. n-1] of X (device int32, strictly increasing; nullptr: rows 0 .. n-1); n <= 1024.

@@ -54,6 +54,15 @@ struct gm_ctx {
   int res_skip = 0;
   // the last Krum call (gm_krum_last_info): {algorithm, candidates, reason}
   int64_t krum_info[3] = {GM_KRUM_EXACT, 0, GM_KRUM_REASON_NOT_CHOSEN};
+  // the last call of a bf16 distance entry (gm_dist_last_info): {tier, reason, slices, flush
+  // width}.  After an MFMA-tier call dist_flag (pinned) receives the device's non-finite flag by
+  // a copy queued on dist_stream; dist_pending until gm_dist_last_info has waited for it, and
+  // dist_exact_slices is what info[2] becomes when the flag is up.
+  int64_t dist_info[4] = {GM_DIST_EXACT, GM_DIST_REASON_REQUESTED_EXACT, 0, 0};
+  int* dist_flag = nullptr;
+  hipStream_t dist_stream = nullptr;
+  bool dist_pending = false;
+  int64_t dist_exact_slices = 0;
 };
 
 namespace gmh {

@@ -5,6 +5,7 @@
 //                   mask, and on request each row's index list
 //   nnm_mix         Y = W X / m from the mask, fp64 sums on the VALU
 #include <algorithm>
+#include <type_traits>
 
 #include "device_util.h"
 #include "gmagg_internal.h"
@@ -86,13 +87,18 @@ constexpr int kMixC = 256;            // columns per block
 constexpr int kMixS = 32;             // rows of X per stage
 constexpr int kMixQ = kMixS * 64 / kMixT;   // float4 groups of a stage per thread
 
-template <int R, bool VEC>
+// T: float, or uint16_t = bf16 bit patterns, which differ in the staging only: a thread loads
+// two 16-byte groups of 8 columns per stage (VEC: base 16-byte aligned, ldx % 8 == 0; else by
+// element) and widens them (exact) on the way into the same fp64 LDS stage.
+template <typename T, int R, bool VEC>
 __global__ void __launch_bounds__(kMixT, 2)
-nnm_mix(const float* __restrict__ X, int64_t K, int64_t d, int64_t ldx, int ws,
+nnm_mix(const T* __restrict__ X, int64_t K, int64_t d, int64_t ldx, int ws,
         const uint32_t* __restrict__ mask, int64_t KW, int64_t m, int64_t nsw, int64_t nblk,
         float* __restrict__ Y, int64_t ldy, int wsy, int vecy) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  constexpr bool B16 = std::is_same<T, uint16_t>::value;
   // the stage widened once, [row][column pair of the lane][lane]: a wave's 16-byte reads and
   // writes are contiguous across lanes
   __shared__ __attribute__((aligned(16))) d2 sX[kMixS][2][64];
@@ -112,7 +118,29 @@ nnm_mix(const float* __restrict__ X, int64_t K, int64_t d, int64_t ldx, int ws,
     for (int e = 0; e < 4; ++e) acc[r][e] = -0.0;
 
   f4 pre[kMixQ];
+  u4 pre16[kMixQ / 2];
   auto load_stage = [&](int64_t st) {
+    if constexpr (B16) {
+#pragma unroll
+      for (int q = 0; q < kMixQ / 2; ++q) {
+        const int idx = threadIdx.x + kMixT * q, r = idx >> 5, cg = idx & 31;
+        const int64_t row = st * kMixS + r, col = j0 + 8 * cg;
+        u4 v = {0u, 0u, 0u, 0u};
+        if (row < K && col < d) {
+          const uint16_t* src = elem(X, ldx, ws, row, col);
+          if (VEC && col + 8 <= d) {
+            v = *reinterpret_cast<const u4*>(src);
+          } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+              const uint32_t h = col + u < d ? (uint32_t)src[u] : 0u;
+              v[u >> 1] |= h << (16 * (u & 1));
+            }
+          }
+        }
+        pre16[q] = v;
+      }
+    } else {
 #pragma unroll
     for (int q = 0; q < kMixQ; ++q) {
       const int idx = threadIdx.x + kMixT * q, r = idx >> 6, cg = idx & 63;
@@ -129,6 +157,7 @@ nnm_mix(const float* __restrict__ X, int64_t K, int64_t d, int64_t ldx, int ws,
       }
       pre[q] = v;
     }
+    }
   };
   // this wave's rows' mask words of stage st, row i0 + r in lane r (rows past K: no members)
   uint32_t nxt = 0u;
@@ -139,11 +168,23 @@ nnm_mix(const float* __restrict__ X, int64_t K, int64_t d, int64_t ldx, int ws,
   load_words(0);
   for (int64_t st = 0; st < nst; ++st) {
     __syncthreads();                                   // the previous stage's reads are done
+    if constexpr (B16) {
+#pragma unroll
+      for (int q = 0; q < kMixQ / 2; ++q) {
+        const int idx = threadIdx.x + kMixT * q, r = idx >> 5, cg = idx & 31;
+#pragma unroll
+        for (int h = 0; h < 4; ++h)                    // word h: columns 8 cg + 2 h, + 1
+          sX[r][h & 1][2 * cg + (h >> 1)] =
+              d2{(double)__uint_as_float(pre16[q][h] << 16),
+                 (double)__uint_as_float(pre16[q][h] & 0xFFFF0000u)};
+      }
+    } else {
 #pragma unroll
     for (int q = 0; q < kMixQ; ++q) {
       const int idx = threadIdx.x + kMixT * q;
       sX[idx >> 6][0][idx & 63] = d2{(double)pre[q][0], (double)pre[q][1]};
       sX[idx >> 6][1][idx & 63] = d2{(double)pre[q][2], (double)pre[q][3]};
+    }
     }
     __syncthreads();
     uint32_t wb[R], any = 0u;
@@ -201,9 +242,10 @@ hipError_t launch_nnm_neighbors(const double* D, int64_t K, int64_t m, uint32_t*
   return hipGetLastError();
 }
 
-hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
-                          const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
-                          hipStream_t s) {
+template <typename T>
+static hipError_t nnm_mix_t(const T* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                            const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
+                            hipStream_t s) {
   if (K < 1 || K > 4096 || m < 1 || m > K) return hipErrorInvalidValue;
   if (d <= 0) return hipSuccess;
   // rows per wave: the fewest that cover K in one sweep, 8 from K = 33 up
@@ -213,15 +255,15 @@ hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int
   if (nblk > 0x7FFFFFF0ll) return hipErrorInvalidValue;
   const dim3 g((unsigned)((nblk + 7) / 8 * 8));
   const int64_t KW = 2 * ((K + 63) / 64);
-  const bool vec = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 4 == 0;
+  const bool vec = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % (16 / sizeof(T)) == 0;
   const int vecy = reinterpret_cast<uintptr_t>(Y) % 16 == 0 && ldy % 4 == 0;
 #define GMK_MIX(R_)                                                                            \
   do {                                                                                         \
     if (vec)                                                                                   \
-      hipLaunchKernelGGL((nnm_mix<R_, true>), g, dim3(kMixT), 0, s, X, K, d, ldx, ws, mask, KW, m, \
+      hipLaunchKernelGGL((nnm_mix<T, R_, true>), g, dim3(kMixT), 0, s, X, K, d, ldx, ws, mask, KW, m, \
                          nsw, nblk, Y, ldy, wsy, vecy);                                        \
     else                                                                                       \
-      hipLaunchKernelGGL((nnm_mix<R_, false>), g, dim3(kMixT), 0, s, X, K, d, ldx, ws, mask, KW, \
+      hipLaunchKernelGGL((nnm_mix<T, R_, false>), g, dim3(kMixT), 0, s, X, K, d, ldx, ws, mask, KW, \
                          m, nsw, nblk, Y, ldy, wsy, vecy);                                     \
   } while (0)
   if (R == 1) GMK_MIX(1);
@@ -230,6 +272,17 @@ hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int
   else GMK_MIX(8);
 #undef GMK_MIX
   return hipGetLastError();
+}
+
+hipError_t launch_nnm_mix(const float* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                          const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
+                          hipStream_t s) {
+  return nnm_mix_t(X, K, d, ldx, ws, mask, m, Y, ldy, wsy, s);
+}
+hipError_t launch_nnm_mix(const uint16_t* X, int64_t K, int64_t d, int64_t ldx, int ws,
+                          const uint32_t* mask, int64_t m, float* Y, int64_t ldy, int wsy,
+                          hipStream_t s) {
+  return nnm_mix_t(X, K, d, ldx, ws, mask, m, Y, ldy, wsy, s);
 }
 
 }  // namespace gmk

@@ -281,6 +281,66 @@ hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, con
   return launch_gather_mean(X, d, ldx, ws, list, m, out, s);
 }
 
+// gather_mean on bf16 bit patterns: 8 consecutive columns per thread (one 16-byte load per
+// listed row; VEC: base 16-byte aligned, ldx % 8 == 0), the ragged last group and the
+// unaligned form one column at a time.  Per column the same fp64 sum in list order.
+template <bool VEC>
+__global__ void __launch_bounds__(256) gather_mean_bf16(const uint16_t* __restrict__ X, int64_t d,
+                                                        int64_t ldx, int ws,
+                                                        const int32_t* __restrict__ list,
+                                                        int64_t m, float* __restrict__ out) {
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  constexpr int W = VEC ? 8 : 1;
+  const int64_t G = (d + W - 1) / W;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j0 = g * W;
+    if (VEC && j0 + 8 <= d) {
+      double s[8];
+      for (int64_t t = 0; t < m; ++t) {
+        const u4 x = *reinterpret_cast<const u4*>(elem(X, ldx, ws, list[t], j0));
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double lo = (double)__uint_as_float(x[v] << 16);
+          const double hi = (double)__uint_as_float(x[v] & 0xFFFF0000u);
+          s[2 * v] = t == 0 ? lo : s[2 * v] + lo;
+          s[2 * v + 1] = t == 0 ? hi : s[2 * v + 1] + hi;
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < 8; ++v) out[j0 + v] = m == 1 ? (float)s[v] : (float)(s[v] / (double)m);
+    } else {
+      for (int v = 0; v < W && j0 + v < d; ++v) {
+        double s = (double)widen(*elem(X, ldx, ws, list[0], j0 + v));
+        for (int64_t t = 1; t < m; ++t) s += (double)widen(*elem(X, ldx, ws, list[t], j0 + v));
+        out[j0 + v] = m == 1 ? (float)s : (float)(s / (double)m);
+      }
+    }
+  }
+}
+
+hipError_t launch_gather_mean(const uint16_t* X, int64_t d, int64_t ldx, int ws,
+                              const int32_t* list, int64_t m, float* out, hipStream_t s) {
+  if (d > 0) {
+    const bool v8 = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 8 == 0;
+    const int64_t items = v8 ? (d + 7) / 8 : d;
+    const dim3 g((unsigned)std::min<int64_t>((items + 255) / 256, 4096));
+    if (v8)
+      hipLaunchKernelGGL(gather_mean_bf16<true>, g, dim3(256), 0, s, X, d, ldx, ws, list, m, out);
+    else
+      hipLaunchKernelGGL(gather_mean_bf16<false>, g, dim3(256), 0, s, X, d, ldx, ws, list, m, out);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_multi_krum_pick(const double* score, int64_t K, int64_t m, const uint16_t* X,
+                                  int64_t d, int64_t ldx, int ws, int32_t* flag, int32_t* list,
+                                  float* out, hipStream_t s) {
+  (void)launch_score_top_m(score, K, m, flag, s);
+  (void)launch_flags_to_list(flag, K, 1, list, s);
+  return launch_gather_mean(X, d, ldx, ws, list, m, out, s);
+}
+
 hipError_t launch_gather_mean(const float* X, int64_t d, int64_t ldx, int ws, const int32_t* list,
                               int64_t m, float* out, hipStream_t s) {
   if (d > 0) {

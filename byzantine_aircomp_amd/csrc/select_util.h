@@ -18,6 +18,16 @@ __device__ __forceinline__ const float* elem(const float* X, int64_t ldx, int ws
                                              int64_t j) {
   return ws ? X + (j >> ws) * ldx + (k << ws) + (j & ((1 << ws) - 1)) : X + k * ldx + j;
 }
+// The same for bf16 bit patterns (bf16 panels: W = 2^ws % 8 == 0, so 8 columns from a multiple
+// of 8 never straddle a panel), and the widening to fp32 (exact).
+__device__ __forceinline__ const uint16_t* elem(const uint16_t* X, int64_t ldx, int ws, int64_t k,
+                                                int64_t j) {
+  return ws ? X + (j >> ws) * ldx + (k << ws) + (j & ((1 << ws) - 1)) : X + k * ldx + j;
+}
+__device__ __forceinline__ float widen(float x) { return x; }
+__device__ __forceinline__ float widen(uint16_t bits) {
+  return __uint_as_float((uint32_t)bits << 16);
+}
 
 __device__ __forceinline__ uint32_t order_key(float x) {
   uint32_t u = __float_as_uint(x);

@@ -506,6 +506,64 @@ int gm_nnm_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx, i
                int64_t f, float* Y, int64_t ldy, int32_t layout_out, int32_t* neighbors,
                void* stream);
 
+/* Krum, Multi-Krum and NNM on bf16 client updates (pairdist_bf16.hip).  X holds bfloat16 bit
+ * patterns, layout GM_LAYOUT_ROWS ([K][ldx], ldx >= d, any 2-byte alignment) or GM_LAYOUT_PANELS
+ * ([ceil(d/W)][K][W], W = gm_panel_width_bf16(K), ldx = panel stride >= K*W); never written.
+ * The outputs are fp32 as for the _f32 entries (gm_nnm_bf16's Y: rows, or fp32 panels of width
+ * gm_panel_width(K)).  dist_mode chooses how the K x K squared distances are made:
+ *
+ *   GM_DIST_EXACT  the fp32 entries' kernels with each element widened at the load (exact).
+ *     Every result (the selected rows, the index, the neighbour lists, out, Y) is the _f32
+ *     entry's on the widened matrix, bit for bit, for both layouts and every alignment.
+ *     (gm_krum_bf16 always takes the exact distance path, whose index the fp32 Gram path
+ *     reproduces by construction.)
+ *
+ *   GM_DIST_MFMA   D~_ij = max(0, G_ii + G_jj - 2 G_ij), D~_ii = 0, from G = X X^T on the bf16
+ *     matrix cores: exact products, fp32 accumulators added into fp64 every C = 256 columns,
+ *     per-slice fp64 partials summed in a fixed order (no atomics: the same bits on every run).
+ *     With D and rho_i = ||x_i||^2 in exact arithmetic on the widened values,
+ *         |D~_ij - D_ij| <= beta (rho_i + rho_j),   beta = (17/8) C 2^-23 = 6.49e-5 <= 2^-13
+ *     (derivation: pairdist_bf16.hip).  Every tile uses the same slices, flush boundaries and
+ *     instruction order, so bit-identical rows get D~ = 0 between them and equal D~ towards
+ *     every third row, and ties go to the lower index as on the exact tier.  The scores, the
+ *     neighbour ranking and the closing passes are unchanged; out / Y are sums of the rows
+ *     themselves, so only the SELECTION can differ from the exact tier, and only between rows
+ *     whose scores or distances lie within the bound.
+ *     Not eligible (rows not 16-byte aligned, or ldx % 8 != 0): the exact tier runs, reason
+ *     GM_DIST_REASON_NOT_ELIGIBLE.  A G_ii that is not finite (a NaN, an infinity, or a square
+ *     that overflows fp32) raises a device flag under which the exact tier's launches, always
+ *     enqueued behind, run instead of returning at once: the result is the exact tier's, bit
+ *     for bit, with no host synchronisation; reason GM_DIST_REASON_NONFINITE.
+ *
+ * gm_pair_dist_bf16 / gm_pair_dist_f32 write the distance matrix on its own: D device fp64
+ * [K][K], full symmetric (fp32: the exact path).
+ * gm_dist_last_info: info[4] = {tier that ran, reason, column slices S, flush width C in
+ * columns (32: the exact tier's fp32 stage)} of this context's last call of one of the bf16
+ * entries, *beta (nullable) the bound's constant.  It waits for the stream of that call.
+ * Limits as the _f32 entries: K <= 4096; d-sharded and collective contexts are refused
+ * (GM_ERR_UNSUPPORTED); d == 0 returns GM_OK (gm_krum_bf16: *index = 0). */
+enum gm_dist_mode { GM_DIST_EXACT = 0, GM_DIST_MFMA = 1 };
+enum gm_dist_reason {
+  GM_DIST_REASON_OK = 0,              /* the tier asked for ran (MFMA) */
+  GM_DIST_REASON_REQUESTED_EXACT = 1, /* exact by request */
+  GM_DIST_REASON_NOT_ELIGIBLE = 2,    /* MFMA asked for on misaligned rows or ldx % 8 != 0 */
+  GM_DIST_REASON_NONFINITE = 3        /* MFMA asked for, a G_ii not finite: the exact tier ran */
+};
+int gm_krum_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                 int32_t layout, int64_t honest_size, int32_t dist_mode, float* out,
+                 int64_t* index, void* stream);
+int gm_multi_krum_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                       int32_t layout, int64_t honest, int64_t m, int32_t dist_mode, float* out,
+                       int32_t* selected, void* stream);
+int gm_nnm_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                int32_t layout_in, int64_t f, int32_t dist_mode, float* Y, int64_t ldy,
+                int32_t layout_out, int32_t* neighbors, void* stream);
+int gm_pair_dist_bf16(gm_ctx* ctx, const uint16_t* X, int64_t K, int64_t d, int64_t ldx,
+                      int32_t layout, int32_t dist_mode, double* D, void* stream);
+int gm_pair_dist_f32(gm_ctx* ctx, const float* X, int64_t K, int64_t d, int64_t ldx,
+                     int32_t layout, double* D, void* stream);
+int gm_dist_last_info(gm_ctx* ctx, int64_t* info, double* beta);
+
 /* Divide-and-Conquer, DnC (Shejwalkar & Houmansadr, "Manipulating the Byzantine: Optimizing Model
  * Poisoning Attacks and Defenses for Federated Learning", NDSS 2021, Algorithm 2): spectral
  * filtering on sampled coordinates, the defence the min-max / min-sum attacks above were
